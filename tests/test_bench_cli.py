@@ -65,6 +65,55 @@ def test_world1_forced_ddp_and_inference():
     assert d["metric"] == "inference images/sec (whole node) ViT-B/16 224px bf16"
 
 
+def test_full_and_dump_outputs_options_parse():
+    bench = _bench()
+    old = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+        a = bench.parse()
+        assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "some/dir"]
+        a = bench.parse()
+        assert a.full is True and a.dump_outputs == "some/dir"
+    finally:
+        sys.argv = old
+
+
+def test_dump_outputs_arrays(tmp_path, monkeypatch):
+    """dump_outputs on a CPU model: float32 .npy files of the loss, logits, gradient norm and the
+    parameters / gradients in model.parameters() order; an array above DUMP_SAMPLE elements is
+    stored as the same seeded sample on every call."""
+    import numpy as np
+    import torch
+
+    bench = _bench()
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(6, 5), torch.nn.Linear(5, 3))
+    logits = model(torch.randn(4, 6))
+    loss = logits.logsumexp(-1).mean()
+    loss.backward()
+    last = {"loss": loss, "logits": logits}
+    shapes = bench.dump_outputs(str(tmp_path / "a"), model, last, grad_norm=torch.tensor(1.5))
+    n = sum(p.numel() for p in model.parameters())
+    assert shapes == {"loss": [1], "logits": [4, 3], "params_sample": [n], "grads_sample": [n], "grad_norm": [1]}
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in shapes}
+    assert all(v.dtype == np.float32 for v in got.values())
+    flat = torch.cat([p.detach().reshape(-1) for p in model.parameters()]).numpy()
+    gflat = torch.cat([p.grad.reshape(-1) for p in model.parameters()]).numpy()
+    assert np.array_equal(got["params_sample"], flat) and np.array_equal(got["grads_sample"], gflat)
+    assert np.array_equal(got["logits"], logits.detach().numpy()) and got["loss"][0] == np.float32(loss.item())
+    assert got["grad_norm"][0] == 1.5
+    # sampling: 16 of the n elements, every one a parameter value, identical from call to call
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 16)
+    s1 = bench.dump_outputs(str(tmp_path / "b"), model, last)
+    s2 = bench.dump_outputs(str(tmp_path / "c"), model, last)
+    assert s1 == s2 and s1["params_sample"] == [16] and s1["logits"] == [4, 3] and "grad_norm" not in s1
+    b, c = np.load(tmp_path / "b" / "params_sample.npy"), np.load(tmp_path / "c" / "params_sample.npy")
+    assert np.array_equal(b, c) and np.isin(b, flat).all() and len(np.unique(b)) > 8
+    # inference: no parameters or gradients
+    assert set(bench.dump_outputs(str(tmp_path / "d"), model, last, training=False)) == {"loss", "logits"}
+
+
 def _run_bench(argv, timeout=420):
     import subprocess
 
@@ -101,3 +150,31 @@ def test_bench_distributed_branch_two_ranks():
     assert j["config"]["parallelism"] == "dp2" and "gloo" in j["config"]["grad_transport"]
     assert j["metric"] == "images/sec (whole node) ViT-B/16 224px bf16 at 1/2/4/8 MI355X"
     assert j["value"] > 0 and abs(j["value"] - 32 * 2 / (j["ms_per_step"] * 2 / 1000.0)) < 0.02 * j["value"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_steps_and_dumped_outputs(tmp_path):
+    """A plain run (`--gpus 1 --steps N --warmup W`, small batch): N timed steps as asked, `ms_per_step`
+    consistent with the headline value, ONE JSON line, and --dump-outputs writes the last step's loss,
+    logits, gradient norm and parameter / gradient samples as finite float32 arrays (non-zero
+    gradients: the fused path's flat gradient buffer is what was sampled)."""
+    import numpy as np
+
+    d = tmp_path / "dump"
+    out = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8", "--dump-outputs", str(d)])
+    lines = _json_lines(out)
+    assert len(lines) == 1, out
+    j = lines[0]
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["n_gpus"] == 1 and j["dtype"] == "bf16"
+    assert j["unit"] == "images/sec" and j["higher_is_better"] is True
+    assert j["metric"] == "images/sec (whole node) ViT-B/16 224px bf16 at 1/2/4/8 MI355X"
+    assert j["ms_per_step"] > 0 and abs(j["value"] - 8 / (j["ms_per_step"] / 1000.0)) < 0.02 * j["value"]
+    arrays = j["dumped_outputs"]["arrays"]
+    assert arrays == {"loss": [1], "logits": [8, 1000], "params_sample": [1 << 20], "grads_sample": [1 << 20],
+                      "grad_norm": [1]}
+    got = {k: np.load(d / f"{k}.npy") for k in arrays}
+    for k, v in got.items():
+        assert v.dtype == np.float32 and list(v.shape) == arrays[k] and np.isfinite(v).all(), k
+    assert abs(float(got["loss"][0]) - j["config"]["final_loss"]) < 1e-3
+    assert got["grad_norm"][0] > 0 and np.count_nonzero(got["grads_sample"]) > (1 << 19)
+    assert np.count_nonzero(got["params_sample"]) > (1 << 19)
