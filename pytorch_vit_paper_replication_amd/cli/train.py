@@ -56,13 +56,19 @@ def build_parser():
                    help="fixed-order reductions instead of float atomics: bitwise-repeatable gradients")
     p.add_argument("--bucket-mb", type=float, default=28.0, help="DDP gradient bucket size (MiB)")
     p.add_argument("--comm-dtype", choices=["fp32", "bf16"], default="fp32", help="DDP all-reduce wire format")
+    p.add_argument("--device-preprocess", action="store_true",
+                   help="ViT: load uint8 images and scale / crop / resize / flip them in the patch-embedding kernel")
+    p.add_argument("--augment", choices=["none", "rrc-flip"], default="none",
+                   help="with --device-preprocess: random-resized-crop + horizontal flip on the device in training")
+    p.add_argument("--source-size", type=int, default=None,
+                   help="with --device-preprocess: side of the uint8 images the loader yields (default: --image-size)")
     return p
 
 
 def main(argv=None) -> int:
     from .. import engine
-    from ..data import create_dataloaders, create_synthetic_dataloaders
-    from ..data.transforms import default_vit_transform
+    from ..data import DeviceInput, RandomResizedCropFlip, create_dataloaders, create_synthetic_dataloaders
+    from ..data.transforms import default_vit_transform, uint8_transform
     from ..models import TinyVGG, vit
     from ..optim import FusedAdam, param_groups_weight_decay, warmup_linear_decay
     from ..parallel import DistributedDataParallel, init_distributed, is_dist
@@ -72,15 +78,20 @@ def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     if args.dtype == "fp8" and args.model == "tinyvgg":
         raise SystemExit("--dtype fp8 applies to the ViT models")
+    if args.device_preprocess and args.model == "tinyvgg":
+        raise SystemExit("--device-preprocess applies to the ViT models")
+    if not args.device_preprocess and (args.augment != "none" or args.source_size is not None):
+        raise SystemExit("--augment and --source-size need --device-preprocess")
+    src_size = args.source_size or args.image_size
     rank, world, device = init_distributed()
     set_seeds(args.seed)
     if args.synthetic or not args.train_dir:
         ncls = args.num_classes or 1000
         train_dl, test_dl, class_names = create_synthetic_dataloaders(
-            args.batch_size, args.synthetic_train_len, args.synthetic_test_len, args.image_size, ncls,
-            num_workers=0)
+            args.batch_size, args.synthetic_train_len, args.synthetic_test_len,
+            src_size if args.device_preprocess else args.image_size, ncls, num_workers=0, uint8=args.device_preprocess)
     else:
-        tf = default_vit_transform(args.image_size)
+        tf = uint8_transform(src_size) if args.device_preprocess else default_vit_transform(args.image_size)
         train_dl, test_dl, class_names = create_dataloaders(args.train_dir, args.test_dir, tf, args.batch_size,
                                                             num_workers=args.num_workers)
     ncls = args.num_classes or len(class_names)
@@ -91,6 +102,11 @@ def main(argv=None) -> int:
         model = vit(args.model, image_size=args.image_size, num_classes=ncls, **drop)
         if args.dtype == "fp8":  # before a resume: the checkpoint's fp8 scaling state needs it
             model.enable_fp8(wgrad=not args.fp8_bf16_wgrad, grad_fmt=args.fp8_grad)
+        if args.device_preprocess:
+            # per-rank crop draws: every rank augments its own shard differently (not saved by --resume)
+            gen = torch.Generator().manual_seed(args.seed * 1_000_003 + rank)
+            aug = RandomResizedCropFlip(generator=gen) if args.augment == "rrc-flip" else None
+            model.set_device_input(DeviceInput(augment=aug))
     model.to(device)
     groups = param_groups_weight_decay(model, args.weight_decay)
     if args.torch_optimizer:

@@ -42,6 +42,8 @@ hipError_t pvr_transpose_batched(const uint16_t*, uint16_t*, const int64_t*, int
 hipError_t pvr_colsum(const uint16_t*, int64_t, int, int, float*, uint16_t*, int64_t, const uint64_t*, uint64_t, uint32_t, float, uint8_t*, int64_t,
                       const float*, unsigned*, int, float*, hipStream_t);
 hipError_t pvr_im2col(const float*, uint16_t*, int, int, int, int, int, int, hipStream_t);
+hipError_t pvr_im2col_u8(const uint8_t*, int64_t, int64_t, int64_t, int64_t, const float*, const float*, const float*, uint16_t*, int, int,
+                         int, int, int, int, int, int, int, hipStream_t);
 hipError_t pvr_cls_rows(const float*, const float*, uint16_t*, int, int, int64_t, const uint64_t*, uint64_t, uint32_t, float, hipStream_t);
 hipError_t pvr_patch_bwd(const uint16_t*, int, int, int, float*, float*, float*, uint16_t*, float*, const uint64_t*, uint64_t, uint32_t, float, hipStream_t);
 int pvr_patch_bwd_groups(int);
@@ -501,6 +503,54 @@ void im2col(torch::Tensor img, torch::Tensor out, int64_t P, int64_t Kp) {
   check(pvr_im2col(f32(img, "img"), bf_mut(out, "out"), (int)img.size(0), (int)img.size(1), (int)img.size(2), (int)img.size(3),
                    (int)P, (int)Kp, stream()),
         "im2col");
+}
+
+// uint8 [B, C <= 4, Hs, Ws] image (any strides: contiguous NCHW, channels_last, views) -> the bf16
+// patch rows of im2col, normalised ((p / 255 - mean[c]) / std[c]) and, with geom [B, 4] float32,
+// cropped / resized / flipped per sample (csrc/elementwise.hip im2col_u8_kernel). Returns 1 when
+// the 8-byte-load path ran, 0 for the per-element path (decided here from data_ptr and strides).
+int64_t im2col_u8(torch::Tensor img, torch::Tensor out, std::vector<double> mean, std::vector<double> stdv,
+                  c10::optional<torch::Tensor> geom, int64_t H, int64_t W, int64_t P, int64_t Kp) {
+  TORCH_CHECK(img.is_cuda() && img.scalar_type() == torch::kUInt8, "im2col_u8: img must be a uint8 GPU tensor, got ",
+              img.scalar_type(), " on ", img.device());
+  TORCH_CHECK(img.dim() == 4, "im2col_u8: img must be [B, C, Hs, Ws], got ", img.dim(), " dims");
+  const int64_t B = img.size(0), C = img.size(1), Hs = img.size(2), Ws = img.size(3);
+  TORCH_CHECK(C >= 1 && C <= 4, "im2col_u8: 1..4 channels, got ", C);
+  TORCH_CHECK((int64_t)mean.size() == C && (int64_t)stdv.size() == C, "im2col_u8: mean / std need one value per channel");
+  for (double sd : stdv) TORCH_CHECK(sd != 0.0, "im2col_u8: std must be non-zero");
+  TORCH_CHECK(P > 0 && H > 0 && W > 0 && H % P == 0 && W % P == 0, "im2col_u8: output ", H, "x", W,
+              " must be a positive multiple of the patch size ", P);
+  TORCH_CHECK(Hs >= 1 && Ws >= 1 && Hs < (1 << 24) && Ws < (1 << 24), "im2col_u8: bad source size ", Hs, "x", Ws);
+  const int64_t rows = B * (H / P) * (W / P);
+  TORCH_CHECK(Kp % 8 == 0 && Kp >= C * P * P, "im2col_u8: Kp must be a multiple of 8 and >= C*P*P");
+  TORCH_CHECK(B < (1ll << 31) && rows < (1ll << 31) && Kp < (1ll << 31), "im2col_u8: sizes exceed 32 bits");
+  TORCH_CHECK(out.is_cuda() && out.device() == img.device() && out.is_contiguous() && out.dim() == 2 && out.size(0) == rows &&
+                  out.size(1) == Kp,
+              "im2col_u8: out must be contiguous bf16 [", rows, ", ", Kp, "] on the image's device");
+  const float* gp = nullptr;
+  if (geom.has_value() && geom->defined()) {
+    TORCH_CHECK(geom->is_cuda() && geom->device() == img.device(), "im2col_u8: geom must be on the image's device");
+    TORCH_CHECK(geom->scalar_type() == torch::kFloat32 && geom->dim() == 2 && geom->size(0) == B && geom->size(1) == 4 &&
+                    geom->is_contiguous(),
+                "im2col_u8: geom must be contiguous float32 [", B, ", 4]");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(geom->data_ptr()) % 16 == 0, "im2col_u8: geom must be 16-byte aligned");
+    gp = geom->data_ptr<float>();
+  } else {
+    TORCH_CHECK(Hs == H && Ws == W, "im2col_u8: a ", Hs, "x", Ws, " source needs geom to produce ", H, "x", W);
+  }
+  const int64_t sb = img.stride(0), sc = img.stride(1), sy = img.stride(2), sx = img.stride(3);
+  TORCH_CHECK(sb >= 0 && sc >= 0 && sy >= 0 && sx >= 0, "im2col_u8: negative strides");
+  const uint8_t* ip = img.data_ptr<uint8_t>();
+  const int vec = !gp && sx == 1 && P % 8 == 0 && reinterpret_cast<uintptr_t>(ip) % 8 == 0 && sb % 8 == 0 && sc % 8 == 0 && sy % 8 == 0;
+  float m[4], sd[4];
+  for (int64_t c = 0; c < C; ++c) {
+    m[c] = (float)mean[c];
+    sd[c] = (float)stdv[c];
+  }
+  check(pvr_im2col_u8(ip, sb, sc, sy, sx, m, sd, gp, bf_mut(out, "out"), (int)B, (int)C, (int)Hs, (int)Ws, (int)H, (int)W, (int)P,
+                      (int)Kp, vec, stream()),
+        "im2col_u8");
+  return vec;
 }
 
 void cls_rows(torch::Tensor cls, torch::Tensor pos, torch::Tensor out, int64_t B, int64_t D, int64_t row_stride,
@@ -1149,6 +1199,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("seed_offset"), py::arg("drop_p"), py::arg("q_out") = py::none(), py::arg("q_scale") = py::none(),
         py::arg("q_amax") = py::none(), py::arg("q_fmt") = 1);
   m.def("im2col", &im2col);
+  m.def("im2col_u8", &im2col_u8, py::arg("img"), py::arg("out"), py::arg("mean"), py::arg("std"), py::arg("geom"), py::arg("H"),
+        py::arg("W"), py::arg("P"), py::arg("Kp"));
   m.def("cls_rows", &cls_rows);
   m.def("patch_bwd", &patch_bwd);
   m.def("xent", &xent, py::arg("logits"), py::arg("labels"), py::arg("dlogits"), py::arg("correct"), py::arg("grad_scale"),

@@ -149,6 +149,115 @@ __global__ void __launch_bounds__(256) im2col_kernel(const float* __restrict__ i
   }
 }
 
+// uint8 source image -> the same bf16 patch rows as im2col_kernel, with the input pipeline's
+// per-image work fused in: scale to [0,1], per-channel normalise and (GEOM) a per-sample crop box
+// resampled bilinearly to H x W, flipped when the box runs right to left.
+//   img  [B][C <= 4][Hs][Ws] uint8 by element strides (sb, sc, sy, sx): contiguous NCHW and
+//        channels_last are both read in place
+//   geom [B][4] = (x0, y0, x1, y1) in source pixel-edge coordinates, x0 > x1 = flipped
+// All arithmetic is fp32 in the order of the PyTorch reference (data/device_input.py
+// preprocess_reference), every operation rounded on its own: contraction is off in this
+// kernel, and the two divisions of ((p / 255) - mean) / std are correctly rounded (hipcc's default;
+// a multiply by 1/255 differs from the division in the last bit for 126 of the 256 byte values).
+// Without GEOM (Hs == H, Ws == W) and with `vec` (host-checked: sx == 1, P % 8 == 0, base and every
+// other stride 8-byte aligned) the 8 pixels of a thread are one 8-byte load; otherwise per element.
+struct U8Norm {
+  float mean[4], stdv[4];
+};
+
+PVR_DEV float u8_normalise(float p, float mean, float stdv) {
+#pragma clang fp contract(off)
+  return (p / 255.0f - mean) / stdv;
+}
+
+// a[c] of a by-value kernel argument without a divergent index into the argument segment
+PVR_DEV float pick4(const float (&a)[4], int c) { return c == 0 ? a[0] : c == 1 ? a[1] : c == 2 ? a[2] : a[3]; }
+
+// Source coordinate of output index o along one axis: box start e0, step = (e1 - e0) / n_out;
+// returns the two taps i <= j (both inside [0, n_src - 1] for any e0 / step, NaN included) and the weight of j.
+PVR_DEV void u8_axis(int o, float e0, float step, int n_src, int& i, int& j, float& w) {
+#pragma clang fp contract(off)
+  float s = e0 + ((float)o + 0.5f) * step - 0.5f;
+  s = fminf(fmaxf(s, 0.f), (float)(n_src - 1));  // fmaxf(NaN, 0) = 0
+  const float f = floorf(s);
+  i = min(max((int)f, 0), n_src - 1);
+  j = min(i + 1, n_src - 1);
+  w = s - f;
+}
+
+template <bool GEOM>
+__global__ void __launch_bounds__(256) im2col_u8_kernel(const uint8_t* __restrict__ img, int64_t sb, int64_t sc, int64_t sy,
+                                                         int64_t sx, U8Norm nrm, const float* __restrict__ geom,
+                                                         uint16_t* __restrict__ out, int B, int C, int Hs, int Ws, int H, int W,
+                                                         int P, int Kp, int vec) {
+#pragma clang fp contract(off)
+  // Without GEOM a pixel is one of 256 byte values: each block tabulates the normalised bf16 of every
+  // (channel, byte) pair once, with the same operations and hence the same bits, and its loop does
+  // no division. Two correctly rounded divisions per element make the kernel ALU-bound: 51 us
+  // against 38 us with the table at 256 x 224 x 224 (the float kernel: 43 us), profiles/input_u8/.
+  __shared__ uint16_t lut[GEOM ? 1 : 4][256];
+  if constexpr (!GEOM) {
+    for (int c = 0; c < C; ++c) lut[c][threadIdx.x] = f2bf(u8_normalise((float)threadIdx.x, nrm.mean[c], nrm.stdv[c]));
+    __syncthreads();
+  }
+  const int gw = W / P, np = (H / P) * gw;
+  const int kc = C * P * P, k8 = Kp / 8;
+  const int64_t total = (int64_t)B * np * k8;
+  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int k0 = (int)(i % k8) * 8;
+    const int64_t rowi = i / k8;
+    const int pidx = (int)(rowi % np);
+    const int b = (int)(rowi / np);
+    const int py = (pidx / gw) * P, px = (pidx % gw) * P;
+    const uint8_t* src_b = img + b * sb;
+    uint32_t h[8];  // bf16 bits
+    if constexpr (!GEOM) {
+      if (vec && k0 + 8 <= kc) {
+        const int c = k0 / (P * P), rem = k0 % (P * P), ph = rem / P, pw = rem % P;
+        const uint2 q = *(const uint2*)(src_b + c * sc + (int64_t)(py + ph) * sy + px + pw);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          h[j] = lut[c][(q.x >> (8 * j)) & 0xFFu];
+          h[4 + j] = lut[c][(q.y >> (8 * j)) & 0xFFu];
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int k = k0 + j;
+          h[j] = 0;
+          if (k < kc) {
+            const int c = k / (P * P), rem = k % (P * P), ph = rem / P, pw = rem % P;
+            h[j] = lut[c][src_b[c * sc + (int64_t)(py + ph) * sy + (int64_t)(px + pw) * sx]];
+          }
+        }
+      }
+    } else {
+      const float4 g = *(const float4*)(geom + (int64_t)b * 4);
+      const float stepx = (g.z - g.x) / (float)W, stepy = (g.w - g.y) / (float)H;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int k = k0 + j;
+        h[j] = 0;
+        if (k < kc) {
+          const int c = k / (P * P), rem = k % (P * P), ph = rem / P, pw = rem % P;
+          const uint8_t* src_c = src_b + c * sc;
+          int xi, xj, yi, yj;
+          float wx, wy;
+          u8_axis(px + pw, g.x, stepx, Ws, xi, xj, wx);
+          u8_axis(py + ph, g.y, stepy, Hs, yi, yj, wy);
+          const float ta = (float)src_c[yi * sy + xi * sx], tb = (float)src_c[yi * sy + xj * sx];
+          const float tc = (float)src_c[yj * sy + xi * sx], td = (float)src_c[yj * sy + xj * sx];
+          const float top = ta + wx * (tb - ta), bot = tc + wx * (td - tc);
+          h[j] = f2bf(u8_normalise(top + wy * (bot - top), pick4(nrm.mean, c), pick4(nrm.stdv, c)));
+        }
+      }
+    }
+    uint4 o;
+    o.x = h[0] | (h[1] << 16); o.y = h[2] | (h[3] << 16); o.z = h[4] | (h[5] << 16); o.w = h[6] | (h[7] << 16);
+    *(uint4*)(out + rowi * Kp + k0) = o;
+  }
+}
+
 // out[b][0][:] = dropout(cls + pos[0])   (row b*(np+1) of the token tensor)
 __global__ void __launch_bounds__(256) cls_rows_kernel(const float* __restrict__ cls, const float* __restrict__ pos,
                                                         uint16_t* __restrict__ out, int B, int D, int64_t row_stride,
@@ -493,6 +602,30 @@ extern "C" hipError_t pvr_im2col(const float* img, uint16_t* out, int B, int C, 
   int64_t blocks = (total + 255) / 256;
   if (blocks > 16384) blocks = 16384;
   hipLaunchKernelGGL(im2col_kernel, dim3((unsigned)blocks), dim3(256), 0, s, img, out, B, C, H, W, P, Kp);
+  return hipGetLastError();
+}
+
+// strides in elements (= bytes); geom null: Hs == H and Ws == W. `vec`: the caller has checked the
+// 8-byte load conditions on the base pointer and strides (bindings.cpp im2col_u8).
+extern "C" hipError_t pvr_im2col_u8(const uint8_t* img, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float* mean,
+                                    const float* stdv, const float* geom, uint16_t* out, int B, int C, int Hs, int Ws, int H,
+                                    int W, int P, int Kp, int vec, hipStream_t s) {
+  using namespace pvr;
+  if (Kp % 8 || P <= 0 || C < 1 || C > 4 || H % P || W % P || Kp < C * P * P || Hs < 1 || Ws < 1) return hipErrorInvalidValue;
+  if (!geom && (Hs != H || Ws != W)) return hipErrorInvalidValue;
+  if (vec && (geom || sx != 1 || P % 8 || reinterpret_cast<uintptr_t>(img) % 8 || sb % 8 || sc % 8 || sy % 8))
+    return hipErrorInvalidValue;
+  const int64_t total = (int64_t)B * (H / P) * (W / P) * (Kp / 8);
+  if (total <= 0) return hipSuccess;
+  int64_t blocks = (total + 255) / 256;
+  if (blocks > 2048) blocks = 2048;  // 8 blocks per CU: a block's 256 x C table entries serve ~9 trips of its threads at b256
+  U8Norm nrm;
+  for (int c = 0; c < 4; ++c) {
+    nrm.mean[c] = c < C ? mean[c] : 0.f;
+    nrm.stdv[c] = c < C ? stdv[c] : 1.f;
+  }
+  hipLaunchKernelGGL(geom ? im2col_u8_kernel<true> : im2col_u8_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, img, sb, sc,
+                     sy, sx, nrm, geom, out, B, C, Hs, Ws, H, W, P, Kp, vec);
   return hipGetLastError();
 }
 

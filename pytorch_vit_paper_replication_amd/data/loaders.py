@@ -51,10 +51,12 @@ def create_dataloaders(train_dir: str, test_dir: str, transform: Callable, batch
 
 
 def create_synthetic_dataloaders(batch_size: int, train_len: int = 256, test_len: int = 64, image_size: int = 224,
-                                 num_classes: int = 1000, num_workers: int = 0, distributed: Optional[bool] = None):
-    """Synthetic stand-in with the same return contract (no dataset download possible offline)."""
-    tr = SyntheticImageNet(train_len, image_size, num_classes, seed=1)
-    te = SyntheticImageNet(test_len, image_size, num_classes, seed=2)
+                                 num_classes: int = 1000, num_workers: int = 0, distributed: Optional[bool] = None,
+                                 uint8: bool = False):
+    """Synthetic stand-in with the same return contract (no dataset download possible offline).
+    ``uint8=True``: raw 0..255 uint8 images of ``image_size`` (the source size of the device-preprocessing path)."""
+    tr = SyntheticImageNet(train_len, image_size, num_classes, seed=1, uint8=uint8)
+    te = SyntheticImageNet(test_len, image_size, num_classes, seed=2, uint8=uint8)
     dist = _dist() if distributed is None else distributed
     return (_make_loader(tr, batch_size, True, num_workers, False, dist),
             _make_loader(te, batch_size, False, num_workers, False, dist), tr.classes)

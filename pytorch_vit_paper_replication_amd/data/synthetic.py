@@ -15,9 +15,10 @@ from torch.utils.data import Dataset
 
 class SyntheticImageNet(Dataset):
     def __init__(self, length: int = 1024, image_size: int = 224, num_classes: int = 1000, channels: int = 3,
-                 seed: int = 0):
+                 seed: int = 0, uint8: bool = False):
         self.length, self.image_size, self.num_classes, self.channels, self.seed = (
             length, image_size, num_classes, channels, seed)
+        self.uint8 = uint8  # raw 0..255 images for the device-preprocessing path (ViT.set_device_input)
         self.classes = [f"class_{i}" for i in range(num_classes)]
 
     def __len__(self):
@@ -25,7 +26,10 @@ class SyntheticImageNet(Dataset):
 
     def __getitem__(self, i):
         g = torch.Generator().manual_seed(self.seed * 1_000_003 + i)
-        x = torch.rand(self.channels, self.image_size, self.image_size, generator=g)
+        if self.uint8:
+            x = torch.randint(0, 256, (self.channels, self.image_size, self.image_size), generator=g, dtype=torch.uint8)
+        else:
+            x = torch.rand(self.channels, self.image_size, self.image_size, generator=g)
         y = int(torch.randint(0, self.num_classes, (1,), generator=g))
         return x, y
 

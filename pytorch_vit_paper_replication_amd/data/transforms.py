@@ -152,6 +152,13 @@ def default_vit_transform(image_size: int = 224) -> Compose:
     return Compose([ToImage(), Resize((image_size, image_size)), ToDtype(torch.float32, scale=True)])
 
 
+def uint8_transform(image_size: int = 224) -> Compose:
+    """Host side of the device-preprocessing pipeline (``ViT.set_device_input``): decode and resize
+    (antialiased) only. Returns uint8 CHW, a quarter of the float tensor's bytes; the default collate
+    stacks it, and scaling, normalisation and augmentation run in the patch-embedding kernel."""
+    return Compose([ToImage(), Resize((image_size, image_size))])
+
+
 def imagenet_eval_transform(image_size: int = 224, resize: int = 256) -> Compose:
     """The pretrained-weights recipe: resize short side, center crop, ImageNet normalisation."""
     return Compose([Resize(resize), CenterCrop(image_size), ToTensor(), Normalize()])

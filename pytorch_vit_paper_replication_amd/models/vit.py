@@ -202,14 +202,74 @@ class ViT(nn.Module):
         x = self.transformer_encoder(x)
         return self.layer_norm(x)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if _ext.use_fused(x) and self._fused_supported(x):
-            return self._forward_fused(x)
+    def forward(self, x: torch.Tensor, geom: Optional[torch.Tensor] = None) -> torch.Tensor:
+        x, pre = self._device_input(x, geom)
+        if _ext.use_fused(x) and self._fused_supported(x, pre):
+            return self._forward_fused(x, pre)
+        x = self._preprocess_reference(x, pre)
         x = self.forward_features(x)
         return self.classifier(x[:, 0])
 
+    # ------------------------------------------------------------------ uint8 input
+    def set_device_input(self, spec) -> "ViT":
+        """Accept raw ``uint8 [B, 3, Hs, Ws]`` batches (contiguous or ``channels_last``): ``spec`` is a
+        :class:`~..data.device_input.DeviceInput` (``None`` turns it off again). Scale to [0, 1],
+        normalisation with ``spec.mean`` / ``spec.std`` and a per-sample crop box ``geom`` resampled to
+        the model's image size run inside the patch-embedding kernel (``im2col_u8``) on the fused
+        path, and as the same fp32 torch ops (``data.device_input.preprocess_reference``) elsewhere.
+
+        ``forward(x, geom=None)``: an explicit ``geom`` (float32 ``[B, 4]`` rows ``(x0, y0, x1, y1)`` in
+        source pixel-edge coordinates, ``x0 > x1`` = flipped) is used as given; in training mode with
+        ``spec.augment`` set the model draws one box per sample from it on the host; otherwise the
+        whole source is resized (nothing at all when the sizes match). The resampling is bilinear
+        without antialiasing: sources more than ~2x the output size alias.
+
+        Float inputs, and uint8 inputs without a spec, run exactly as before."""
+        object.__setattr__(self, "_device_input_spec", spec)
+        return self
+
+    def _device_input(self, x: torch.Tensor, geom: Optional[torch.Tensor]):
+        """``(x, pre)``: ``pre`` is None for the float path, else ``(mean, std, geom or None)`` of a
+        uint8 batch to preprocess on the device (geom already there, float32 ``[B, 4]``)."""
+        spec = getattr(self, "_device_input_spec", None)
+        if spec is None or x.dtype != torch.uint8:
+            if geom is not None:
+                raise ValueError("forward(geom=...) needs a uint8 batch and set_device_input(spec)")
+            return x, None
+        if x.dim() != 4:
+            raise ValueError(f"uint8 input must be [B, C, Hs, Ws], got {tuple(x.shape)}")
+        B, C, Hs, Ws = x.shape
+        S = self.config["image_size"]
+        mean, std = spec.mean_std(C)
+        if geom is None:
+            if self.training and spec.augment is not None:
+                if x.is_cuda and torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("device-input augmentation draws its crop boxes on the host every step: it cannot "
+                                       "run inside a graph capture (a replay would reuse one draw); pass geom explicitly "
+                                       "or train without --graph")
+                geom = spec.augment.sample(B, Hs, Ws)
+                if x.is_cuda:
+                    geom = geom.pin_memory()
+            elif (Hs, Ws) != (S, S):
+                from ..data.device_input import full_box
+
+                geom = full_box(B, Hs, Ws)
+        if geom is not None:
+            if tuple(geom.shape) != (B, 4):
+                raise ValueError(f"geom must be [{B}, 4] (x0, y0, x1, y1) rows, got {tuple(geom.shape)}")
+            geom = geom.to(device=x.device, dtype=torch.float32, non_blocking=True).contiguous()
+        return x, (mean, std, geom)
+
+    def _preprocess_reference(self, x: torch.Tensor, pre) -> torch.Tensor:
+        if pre is None:
+            return x
+        from ..data.device_input import preprocess_reference
+
+        S = self.config["image_size"]
+        return preprocess_reference(x, pre[0], pre[1], pre[2], (S, S))
+
     # ------------------------------------------------------------------ fused path
-    def _fused_supported(self, x: torch.Tensor) -> bool:
+    def _fused_supported(self, x: torch.Tensor, pre=None) -> bool:
         c = self.config
         D, H = c["embedding_dim"], c["num_heads"]
         if x.dim() != 4 or x.shape[1] != 3 or D % H != 0 or D // H not in (64, 80, 96, 128) or D % 64 != 0:
@@ -217,6 +277,8 @@ class ViT(nn.Module):
         if c["mlp_size"] % 64 != 0:
             return False
         P = c["patch_size"]
+        if pre is not None:  # uint8 input: the kernel produces image_size x image_size from any source size
+            return c["image_size"] % P == 0
         return x.shape[2] == x.shape[3] == c["image_size"] and x.shape[2] % P == 0
 
     @staticmethod
@@ -241,18 +303,19 @@ class ViT(nn.Module):
         _ext.ext().rng_next(rng, seed)  # seed = rng; rng += 1 (one device kernel, graph-replay safe)
         return seed
 
-    def _forward_fused(self, x: torch.Tensor) -> torch.Tensor:
+    def _forward_fused(self, x: torch.Tensor, pre=None) -> torch.Tensor:
         from ..ops.fused_vit import HeadFn
 
-        tokens, store, B, N = self._fused_encoder(x)
+        tokens, store, B, N = self._fused_encoder(x, pre)
         head = self.classifier[0]
         return HeadFn.apply(tokens, B, N, self.layer_norm.eps, store, self.layer_norm.weight, self.layer_norm.bias,
                             head.weight, head.bias)
 
-    def _fused_encoder(self, x: torch.Tensor):
+    def _fused_encoder(self, x: torch.Tensor, pre=None):
         """Patch embedding + every encoder block on the fused path: (bf16 tokens [B*N, D], store, B, N).
-        Shared by this model's head and the classifier-free backbone (models/vit_no_classifier.py)."""
-        from ..ops.fused_vit import ATTN_SITE, EncoderBlockFn, block_links, PatchEmbedFn, site_drop
+        Shared by this model's head and the classifier-free backbone (models/vit_no_classifier.py).
+        ``pre`` = ``(mean, std, geom)`` of a uint8 batch (:meth:`_device_input`), None for a float one."""
+        from ..ops.fused_vit import ATTN_SITE, EncoderBlockFn, block_links, PatchEmbedFn, PatchEmbedU8Fn, site_drop
         from ..runtime.param_store import get_store
 
         c = self.config
@@ -276,8 +339,14 @@ class ViT(nn.Module):
         seed = self._dropout_seed(dev) if need_seed else None
         pe = self.patch_embedding_block
         conv = pe.patch_and_flatten[0]
-        tokens = PatchEmbedFn.apply(x, c["patch_size"], store, seed, pe.dropout.p, training,
-                                    conv.weight, conv.bias, pe.class_token, pe.position_embedding)
+        if pre is None:
+            tokens = PatchEmbedFn.apply(x, c["patch_size"], store, seed, pe.dropout.p, training,
+                                        conv.weight, conv.bias, pe.class_token, pe.position_embedding)
+        else:
+            mean, std, geom = pre
+            tokens = PatchEmbedU8Fn.apply(x, geom, mean, std, (c["image_size"], c["image_size"]), c["patch_size"], store, seed,
+                                          pe.dropout.p, training, conv.weight, conv.bias, pe.class_token,
+                                          pe.position_embedding)
         B = x.shape[0]
         N = pe.number_of_patches + 1
         f8 = self._fp8_state(dev, B * N)

@@ -6,6 +6,8 @@ verbatim copies; here there is one implementation).
 """
 from __future__ import annotations
 
+from typing import Optional
+
 import torch
 from torch import nn
 
@@ -24,14 +26,15 @@ class ViT(_FullViT):
         del self.classifier
         self.config.pop("num_classes", None)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if _ext.use_fused(x) and self._fused_supported(x):
-            return self._forward_fused_features(x)
-        return self.forward_features(x)
+    def forward(self, x: torch.Tensor, geom: Optional[torch.Tensor] = None) -> torch.Tensor:
+        x, pre = self._device_input(x, geom)  # uint8 batches after set_device_input (models/vit.py)
+        if _ext.use_fused(x) and self._fused_supported(x, pre):
+            return self._forward_fused_features(x, pre)
+        return self.forward_features(self._preprocess_reference(x, pre))
 
-    def _forward_fused_features(self, x: torch.Tensor) -> torch.Tensor:
+    def _forward_fused_features(self, x: torch.Tensor, pre=None) -> torch.Tensor:
         from ..ops.fused_vit import TokenLayerNormFn
 
-        tokens, store, B, N = self._fused_encoder(x)  # the full ViT's fused encoder (device checks, side-stream join)
+        tokens, store, B, N = self._fused_encoder(x, pre)  # the full ViT's fused encoder (device checks, side-stream join)
         y = TokenLayerNormFn.apply(tokens, self.layer_norm.eps, store, self.layer_norm.weight, self.layer_norm.bias)
         return y.float().view(B, N, -1)

@@ -38,55 +38,92 @@ def site_drop(seed: Optional[torch.Tensor], site: int, p: float, training: bool)
     return (seed, site << SITE_SHIFT, float(p))
 
 
+def _patch_geometry(C, H, W, patch):
+    n_p = (H // patch) * (W // patch)
+    kc = C * patch * patch
+    return n_p, kc, (kc + 63) // 64 * 64
+
+
+def _patch_embed_fwd(ctx, patches, B, n_p, kc, kp, store, seed, p_drop, training, conv_w, conv_b, cls, pos):
+    """Patch rows [B*n_p, kp] bf16 -> tokens [B*(n_p+1), D]: the embedding GEMM with the position
+    addend and dropout, the CLS rows, and what the backward needs. Shared by the float and the
+    uint8 entry (PatchEmbedFn / PatchEmbedU8Fn), which differ only in how ``patches`` is built."""
+    ext = _ext.ext()
+    dev = patches.device
+    D = conv_w.shape[0]
+    ntok = n_p + 1
+    w16 = store.bf16(conv_w).reshape(D, kc)
+    if kp != kc:
+        if kc % 4 == 0:
+            w16p = torch.empty(D, kp, dtype=torch.bfloat16, device=dev)
+            ext.pad_cols_bf16(w16, w16p)  # 8-B column groups
+            w16 = w16p
+        else:  # odd patch sizes (kc = 3 * P * P odd): plain zero padding
+            w16 = torch.nn.functional.pad(w16, (0, kp - kc))
+    tokens = torch.empty(B * ntok, D, dtype=torch.bfloat16, device=dev)
+    drop = site_drop(seed, 0, p_drop, training)
+    gemm.linear_fwd(patches, w16, conv_b, addend=pos.reshape(ntok, D), addend_period=ntok,
+                    row_remap=(n_p, ntok, 1), drop=drop, out=tokens)
+    dseed, doff, dp = gemm._drop_args(drop)
+    ext.cls_rows(cls.reshape(D), pos.reshape(ntok, D)[0].contiguous(), tokens, B, D, ntok * D, dseed, doff, dp)
+    ctx.save_for_backward(patches)
+    ctx.meta = (store, drop, B, ntok, D, kc, kp, conv_w, conv_b, cls, pos)
+    return tokens
+
+
+def _patch_embed_bwd(ctx, dtokens) -> None:
+    ext = _ext.ext()
+    (patches,) = ctx.saved_tensors
+    store, drop, B, ntok, D, kc, kp, conv_w, conv_b, cls, pos = ctx.meta
+    dtokens = dtokens.contiguous()
+    gpos = store.grad_dest(pos)
+    gcls = store.grad_dest(cls)
+    gb = store.grad_dest(conv_b)
+    gw = store.grad_dest(conv_w)
+    dconv = torch.empty(B * (ntok - 1), D, dtype=torch.bfloat16, device=dtokens.device) if gw is not None else None
+    dseed, doff, dp = gemm._drop_args(drop)
+    ext.patch_bwd(dtokens, B, ntok, D, None if gpos is None else gpos.view(-1),
+                  None if gcls is None else gcls.view(-1), dconv, gb, dseed, doff, dp)
+    if gw is not None:  # K padded to kp in patches; the reduction writes the first kc columns
+        gemm.linear_wgrad(dconv, patches, gw.view(D, kc))
+    store.grad_ready([conv_w, conv_b, cls, pos])
+
+
 class PatchEmbedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, patch, store, seed, p_drop, training, conv_w, conv_b, cls, pos):
-        ext = _ext.ext()
         img = img.float().contiguous()
         B, C, H, W = img.shape
-        D = conv_w.shape[0]
-        n_p = (H // patch) * (W // patch)
-        ntok = n_p + 1
-        kc = C * patch * patch
-        kp = (kc + 63) // 64 * 64
+        n_p, kc, kp = _patch_geometry(C, H, W, patch)
         patches = torch.empty(B * n_p, kp, dtype=torch.bfloat16, device=img.device)
-        ext.im2col(img, patches, patch, kp)
-        w16 = store.bf16(conv_w).reshape(D, kc)
-        if kp != kc:
-            if kc % 4 == 0:
-                w16p = torch.empty(D, kp, dtype=torch.bfloat16, device=img.device)
-                ext.pad_cols_bf16(w16, w16p)  # 8-B column groups
-                w16 = w16p
-            else:  # odd patch sizes (kc = 3 * P * P odd): plain zero padding
-                w16 = torch.nn.functional.pad(w16, (0, kp - kc))
-        tokens = torch.empty(B * ntok, D, dtype=torch.bfloat16, device=img.device)
-        drop = site_drop(seed, 0, p_drop, training)
-        gemm.linear_fwd(patches, w16, conv_b, addend=pos.reshape(ntok, D), addend_period=ntok,
-                        row_remap=(n_p, ntok, 1), drop=drop, out=tokens)
-        dseed, doff, dp = gemm._drop_args(drop)
-        ext.cls_rows(cls.reshape(D), pos.reshape(ntok, D)[0].contiguous(), tokens, B, D, ntok * D, dseed, doff, dp)
-        ctx.save_for_backward(patches)
-        ctx.meta = (store, drop, B, ntok, D, kc, kp, conv_w, conv_b, cls, pos)
-        return tokens
+        _ext.ext().im2col(img, patches, patch, kp)
+        return _patch_embed_fwd(ctx, patches, B, n_p, kc, kp, store, seed, p_drop, training, conv_w, conv_b, cls, pos)
 
     @staticmethod
     def backward(ctx, dtokens):
-        ext = _ext.ext()
-        (patches,) = ctx.saved_tensors
-        store, drop, B, ntok, D, kc, kp, conv_w, conv_b, cls, pos = ctx.meta
-        dtokens = dtokens.contiguous()
-        gpos = store.grad_dest(pos)
-        gcls = store.grad_dest(cls)
-        gb = store.grad_dest(conv_b)
-        gw = store.grad_dest(conv_w)
-        dconv = torch.empty(B * (ntok - 1), D, dtype=torch.bfloat16, device=dtokens.device) if gw is not None else None
-        dseed, doff, dp = gemm._drop_args(drop)
-        ext.patch_bwd(dtokens, B, ntok, D, None if gpos is None else gpos.view(-1),
-                      None if gcls is None else gcls.view(-1), dconv, gb, dseed, doff, dp)
-        if gw is not None:  # K padded to kp in patches; the reduction writes the first kc columns
-            gemm.linear_wgrad(dconv, patches, gw.view(D, kc))
-        store.grad_ready([conv_w, conv_b, cls, pos])
+        _patch_embed_bwd(ctx, dtokens)
         return (None,) * 10
+
+
+class PatchEmbedU8Fn(torch.autograd.Function):
+    """PatchEmbedFn for a raw uint8 image batch [B, C, Hs, Ws] (contiguous or channels_last, read in
+    place): ``im2col_u8`` scales to [0, 1], normalises with ``mean`` / ``std`` (per-channel tuples) and,
+    with ``geom`` [B, 4] float32 on the device, crops / resizes / flips each sample to ``size`` = (H, W)
+    while it writes the patch rows (data/device_input.py). ``geom`` None needs Hs x Ws == H x W."""
+
+    @staticmethod
+    def forward(ctx, img, geom, mean, std, size, patch, store, seed, p_drop, training, conv_w, conv_b, cls, pos):
+        B, C = img.shape[0], img.shape[1]
+        H, W = size
+        n_p, kc, kp = _patch_geometry(C, H, W, patch)
+        patches = torch.empty(B * n_p, kp, dtype=torch.bfloat16, device=img.device)
+        _ext.ext().im2col_u8(img, patches, list(mean), list(std), geom, H, W, patch, kp)
+        return _patch_embed_fwd(ctx, patches, B, n_p, kc, kp, store, seed, p_drop, training, conv_w, conv_b, cls, pos)
+
+    @staticmethod
+    def backward(ctx, dtokens):
+        _patch_embed_bwd(ctx, dtokens)
+        return (None,) * 14
 
 
 # test hook: bf16 outputs left unwritten on the fp8 path (only their fp8 copies are consumed) are
