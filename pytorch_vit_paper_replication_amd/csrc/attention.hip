@@ -25,6 +25,7 @@
 // last key's dS / dK / dV. Heads with more keys accumulate dQ in f32 slabs (or atomics) that the
 // tail launch's final pass turns into bf16 dQ, its optional fp8 (e5m2 / e4m3) copy and the q-bias partials.
 #include "attn_common.h"
+#include "kernels.h"
 
 namespace pvr {
 namespace {
@@ -1684,7 +1685,6 @@ __global__ void __launch_bounds__(256) dbias_final_kernel(const float* __restric
 }  // namespace
 }  // namespace pvr
 
-// ws: f32 [S][H][2 * DH] scratch, S = pvr_attn_dbias_splits(B, NQ); part f32 [B*H][NQ][3 * DH]
 extern "C" int pvr_attn_dbias_splits(int B, int NQ) { return B * NQ < 128 ? B * NQ : 128; }
 
 extern "C" hipError_t pvr_attn_dbias_reduce(const float* part, float* ws, float* dbias, int B, int H, int NQ, int D, hipStream_t s) {
@@ -1801,7 +1801,6 @@ static hipError_t attn_fwd_launch(const uint16_t* qkv, int64_t ld, uint16_t* out
   return attn_fwd_tiled_pick<DH, false>(qkv, ld, out, ld_o, lse, B, N, H, D, scale, drop, q8, s);
 }
 
-// diagnostic builds (-DPVR_ATTN_STAMPS): where the backward writes its phase stamps (null: nowhere)
 extern "C" void pvr_set_attn_dbg(void* p) {
 #ifdef PVR_ATTN_STAMPS
   uint64_t* q = (uint64_t*)p;
@@ -1818,18 +1817,15 @@ extern "C" void pvr_set_attn_fwd_head_qf(int qf) { g_attn_fwd_head_qf = qf == 2 
 static int g_attn_prep_xcd = 0;
 extern "C" void pvr_set_attn_prep_xcd(int on) { g_attn_prep_xcd = on ? 1 : 0; }
 
-// seed (optional): attention-probability dropout with keep threshold thr16 (see AttnDrop); the
-// backward must get the same seed / seed_off / thr16
 extern "C" hipError_t pvr_attn_fwd(const uint16_t* qkv, int64_t ld, uint16_t* out, int64_t ld_o, float* lse, int B, int N,
-                                   int H, int D, float scale, const uint64_t* seed, uint64_t seed_off, uint32_t thr16, float keep_scale,
-                                   uint8_t* q8_out, int64_t q8_ld, const float* q8_qs, unsigned* q8_amax, int q8_only, hipStream_t s) {
+                                   int H, int D, float scale, pvr::DropSite site, pvr::Fp8Copy c8, int q8_only, hipStream_t s) {
   using namespace pvr;
   if (H <= 0 || D % H != 0 || B <= 0 || N <= 0 || N > 65536) return hipErrorInvalidValue;
-  if (q8_out && (!q8_qs || !q8_amax || q8_ld % 4 != 0 || (uintptr_t)q8_out % 4 != 0)) return hipErrorInvalidValue;
-  if (q8_only && !q8_out) return hipErrorInvalidValue;
-  const AttnDrop drop{seed, seed_off, thr16, keep_scale};
+  if (c8.out && (!c8.scale || !c8.amax || c8.ld % 4 != 0 || (uintptr_t)c8.out % 4 != 0)) return hipErrorInvalidValue;
+  if (q8_only && !c8.out) return hipErrorInvalidValue;
+  const AttnDrop drop{site.seed, site.offset, site.thr, site.scale};
   // only (inference): O's e4m3 copy alone is stored (bf16 O unwritten); the copy's path is the generic kernel
-  const AttnQ8 q8{q8_out, q8_ld, q8_qs, q8_amax, q8_only ? 1 : 0};
+  const AttnQ8 q8{c8.out, c8.ld, c8.scale, c8.amax, q8_only ? 1 : 0};
   switch (D / H) {
     case 64: return attn_fwd_launch<64>(qkv, ld, out, ld_o, lse, B, N, H, D, scale, drop, q8, s);
     case 80: return attn_fwd_launch<80>(qkv, ld, out, ld_o, lse, B, N, H, D, scale, drop, q8, s);
@@ -1841,7 +1837,6 @@ extern "C" hipError_t pvr_attn_fwd(const uint16_t* qkv, int64_t ld, uint16_t* ou
 
 extern "C" int pvr_attn_head_dim_supported(int dh) { return dh == 64 || dh == 80 || dh == 96 || dh == 128; }
 
-extern "C" int pvr_attn_bwd_waves(int N);
 extern "C" int pvr_attn_bwd_key_blocks(int N) {
   const int kb = 32 * pvr_attn_bwd_waves(N);
   return (N + kb - 1) / kb;
@@ -1887,8 +1882,6 @@ static bool attn_bwd_bpart_ok(int N, int DH) {
   return (N + KB - 1) / KB == 1 && NE <= pvr_attn_bwd_waves(N);
 }
 
-// 1 if pvr_attn_bwd needs the zero-initialised f32 dQ workspace for this shape (det: deterministic
-// mode, where such shapes sum per-key-block dQ slabs in a fixed order instead: no workspace)
 extern "C" int pvr_attn_bwd_needs_dq_acc(int N, int dh, int dbias, int drop, int det) {
   if (pvr_attn_bwd_key_blocks(N) <= 1 || det) return 0;
   return attn_bwd_lastkey_path(N, dbias != 0, drop != 0) || attn_bwd_slab_path(N, dbias != 0, drop != 0) ? 0 : 1;
@@ -2022,8 +2015,6 @@ static hipError_t attn_bwd_launch(const uint16_t* qkv, int64_t ld, const uint16_
                                      drop, q8, s);
 }
 
-// floats of the f32 scratch pvr_attn_bwd needs (per-query delta and, on the lastkey path, ds_last;
-// dQ slabs on the tail-split path, and in deterministic mode (det) on multi-key-block shapes without it)
 extern "C" int64_t pvr_attn_bwd_ws_floats(int B, int N, int H, int D, int dbias, int drop, int det) {
   int64_t n = 2 * (int64_t)B * H * N;
   const int KB = 32 * pvr_attn_bwd_waves(N);
@@ -2034,50 +2025,31 @@ extern "C" int64_t pvr_attn_bwd_ws_floats(int B, int N, int H, int D, int dbias,
   return n;
 }
 
-// 1 if pvr_attn_bwd can write dQKV's e5m2 copy (q8_out) for this shape: the generic kernels must
-// write every final dQ value
 extern "C" int pvr_attn_bwd_q8_ok(int N, int drop) { return attn_bwd_final_dq_in_kernel(N, false, drop != 0) ? 1 : 0; }
 
-// 1 if pvr_attn_bwd takes the pipelined whole-head backward for this shape and these layouts; its
-// dbias is then f32 [B*H][ceil(N/32)][192] partials instead: per (batch, head, 32-query block) the
-// column sums of dQ over its two 16-query halves (2 x 64, the head's q-bias slice; summed) and of dO
-// (64: the v-bias slice, sum_k dV = sum_q dO since softmax rows sum to 1); the k-bias gradient is
-// exactly 0 (sum_k dS = 0 per query)
 extern "C" int pvr_attn_bwd_uses_pipe(int B, int N, int H, int D, int64_t ld, int64_t ld_do, int64_t ld_o, int64_t ld_dq, int drop) {
   return !drop && attn_bwd_pipe_ok(B, N, H, D, ld, ld_do, ld_o, ld_dq) ? 1 : 0;
 }
 
-// Rows R of the f32 [B*H][R][3*dh] bias-gradient partials (q half 0 | q half 1 | v) that pvr_attn_bwd
-// writes for this shape: pipelined kernel (into `dbias`): R = 32-query blocks; generic kernel (into
-// `bpart`): R = 1 where attn_bwd_bpart_ok; 0: none (`dbias` then means the generic kernel's
-// [B * key blocks][3D] layout).
 extern "C" int pvr_attn_bwd_part_rows(int B, int N, int H, int D, int64_t ld, int64_t ld_do, int64_t ld_o, int64_t ld_dq, int drop) {
   if (pvr_attn_bwd_uses_pipe(B, N, H, D, ld, ld_do, ld_o, ld_dq, drop)) return (N + 31) / 32;
   return !drop && H > 0 && D % H == 0 && pvr_attn_head_dim_supported(D / H) && attn_bwd_bpart_ok(N, D / H) ? 1 : 0;
 }
 
-// dq_acc: f32 [B*N][D] zero-initialised workspace, required iff N > 256 (several key blocks per head);
-// dq_rezero = 1 leaves it zeroed again afterwards (a persistent workspace reused across calls).
-// dbias: optional f32 [B * nkb][3D] partial column sums of dQ | dK | dV (nkb = pvr_attn_bwd_key_blocks;
-// every element is written), whose row sum is the in_proj bias gradient; on the pipelined path
-// (pvr_attn_bwd_uses_pipe) the per-block partials described there.
-// ws: f32 scratch of pvr_attn_bwd_ws_floats(B, N, H) floats (the generic path's pre-pass outputs).
-extern "C" hipError_t pvr_attn_bwd(const uint16_t* qkv, int64_t ld, const uint16_t* out, int64_t ld_o, const uint16_t* dout,
-                                   int64_t ld_do, const float* lse, uint16_t* dqkv, int64_t ld_dq, float* dq_acc,
-                                   int dq_rezero, float* dbias, float* bpart, float* ws, int B, int N, int H, int D, float scale,
-                                   const uint64_t* seed, uint64_t seed_off, uint32_t thr16, float keep_scale, uint8_t* q8_out,
-                                   int64_t q8_ld, const float* q8_qs, unsigned* q8_amax, int q8_only, int q8_fmt, hipStream_t s) {
-  if (H <= 0 || D % H != 0 || B <= 0 || N <= 0 || N > 65536) return hipErrorInvalidValue;
-  if (q8_fmt != 0 && q8_fmt != 1) return hipErrorInvalidValue;
-  if (q8_out && (!q8_qs || !q8_amax || q8_ld % 4 != 0 || (uintptr_t)q8_out % 4 != 0)) return hipErrorInvalidValue;
-  const pvr::AttnDrop drop{seed, seed_off, thr16, keep_scale};
-  if (q8_only && !q8_out) return hipErrorInvalidValue;
-  const pvr::AttnQ8 q8{q8_out, q8_ld, q8_qs, q8_amax, q8_only, q8_fmt};
-  switch (D / H) {
+extern "C" hipError_t pvr_attn_bwd(const pvr::AttnBwdParams* pp, hipStream_t s) {
+  const pvr::AttnBwdParams& p = *pp;
+  const pvr::Fp8Copy& c8 = p.q8;
+  if (p.H <= 0 || p.D % p.H != 0 || p.B <= 0 || p.N <= 0 || p.N > 65536) return hipErrorInvalidValue;
+  if (c8.fmt != 0 && c8.fmt != 1) return hipErrorInvalidValue;
+  if (c8.out && (!c8.scale || !c8.amax || c8.ld % 4 != 0 || (uintptr_t)c8.out % 4 != 0)) return hipErrorInvalidValue;
+  const pvr::AttnDrop drop{p.drop.seed, p.drop.offset, p.drop.thr, p.drop.scale};
+  if (p.q8_only && !c8.out) return hipErrorInvalidValue;
+  const pvr::AttnQ8 q8{c8.out, c8.ld, c8.scale, c8.amax, p.q8_only, c8.fmt};
+  switch (p.D / p.H) {
 #define PVR_BWD_DH(DH) \
   case DH:             \
-    return attn_bwd_launch<DH>(qkv, ld, out, ld_o, dout, ld_do, lse, dqkv, ld_dq, dq_acc, dq_rezero, dbias, bpart, ws, B, N, H, D, scale, \
-                               drop, q8, s);
+    return attn_bwd_launch<DH>(p.qkv, p.ld, p.out, p.ld_o, p.dout, p.ld_do, p.lse, p.dqkv, p.ld_dq, p.dq_acc, p.dq_rezero, p.dbias, p.bpart, p.ws, \
+                               p.B, p.N, p.H, p.D, p.scale, drop, q8, s);
     PVR_BWD_DH(64) PVR_BWD_DH(80) PVR_BWD_DH(96) PVR_BWD_DH(128)
 #undef PVR_BWD_DH
     default: return hipErrorInvalidValue;

@@ -8,86 +8,7 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
-#include "gemm_params.h"
-
-
-namespace pvr {
-
-struct AdamGroup {
-  float lr, beta1, beta2, eps, weight_decay;
-  float bc1, bc2_sqrt;
-  int decoupled;
-};
-}  // namespace pvr
-
-extern "C" {
-hipError_t pvr_gemm(const pvr::GemmParams* p, hipStream_t s);
-int pvr_gemm_tail_split(int M, int N, int K, int elem_bytes, int max_units);
-void pvr_set_attn_fwd_qg(int qg);
-void pvr_set_attn_fwd_head_qf(int qf);
-void pvr_set_ln_fwd_q8_grid(int per_cu);
-void pvr_set_attn_prep_xcd(int on);
-void pvr_set_attn_dbg(void* p);
-void pvr_set_fp8_persistent(int mode);
-hipError_t pvr_layernorm_fwd(const uint16_t*, int64_t, const float*, const float*, uint16_t*, int64_t, float*, float*, int, int, float, hipStream_t);
-hipError_t pvr_layernorm_fwd_q8(const uint16_t*, int64_t, const float*, const float*, uint16_t*, int64_t, uint8_t*, int64_t, const float*,
-                                unsigned*, float*, float*, int, int, float, hipStream_t);
-hipError_t pvr_layernorm_bwd(const uint16_t*, int64_t, const uint16_t*, int64_t, const float*, const float*, const float*, const uint16_t*, int64_t, uint16_t*, int64_t, float*, float*, float*, uint16_t*, int64_t, const uint64_t*, uint64_t, uint32_t, float, int, uint8_t*, int64_t, const float*, unsigned*, int, int, int, float*, hipStream_t);
-int pvr_layernorm_bwd_blocks(int, int);
-int pvr_colsum_part_rows(int);
-hipError_t pvr_cast_f32_bf16(const float*, uint16_t*, int64_t, hipStream_t);
-hipError_t pvr_splitk_reduce(const float*, int, int64_t, float*, int64_t, int, int, int, hipStream_t);
-hipError_t pvr_pad_cols_bf16(const uint16_t*, int, int, uint16_t*, int, hipStream_t);
-hipError_t pvr_transpose_batched(const uint16_t*, uint16_t*, const int64_t*, int, int, hipStream_t);
-hipError_t pvr_colsum(const uint16_t*, int64_t, int, int, float*, uint16_t*, int64_t, const uint64_t*, uint64_t, uint32_t, float, uint8_t*, int64_t,
-                      const float*, unsigned*, int, float*, hipStream_t);
-hipError_t pvr_im2col(const float*, uint16_t*, int, int, int, int, int, int, hipStream_t);
-hipError_t pvr_im2col_u8(const uint8_t*, int64_t, int64_t, int64_t, int64_t, const float*, const float*, const float*, uint16_t*, int, int,
-                         int, int, int, int, int, int, int, hipStream_t);
-hipError_t pvr_cls_rows(const float*, const float*, uint16_t*, int, int, int64_t, const uint64_t*, uint64_t, uint32_t, float, hipStream_t);
-hipError_t pvr_patch_bwd(const uint16_t*, int, int, int, float*, float*, float*, uint16_t*, float*, const uint64_t*, uint64_t, uint32_t, float, hipStream_t);
-int pvr_patch_bwd_groups(int);
-int64_t pvr_patch_bwd_ws_floats(int, int, int);
-hipError_t pvr_head_fwd(const uint16_t*, int64_t, int, int, const float*, const float*, float, const float*, const float*, int, float*, float*,
-                        float*, hipStream_t);
-hipError_t pvr_head_bwd(const float*, const float*, const float*, const float*, const float*, const float*, int, int, int, int, float*,
-                        float*, float*, float*, float*, uint16_t*, float*, hipStream_t);
-hipError_t pvr_scale_by(const float*, const float*, float*, int64_t, hipStream_t);
-hipError_t pvr_mean(const float*, int, float*, hipStream_t);
-hipError_t pvr_metrics_accum(float*, const float*, const int*, int, hipStream_t);
-hipError_t pvr_rng_next(int64_t*, int64_t*, hipStream_t);
-hipError_t pvr_zero_f32(float*, int64_t, hipStream_t);
-hipError_t pvr_xent(const float*, int64_t, const int64_t*, int, int, float*, float*, int*, float, hipStream_t);
-int pvr_norm_partial_blocks();
-hipError_t pvr_grad_norm(const float*, int64_t, float, float*, float*, hipStream_t);
-hipError_t pvr_adam(float*, const float*, float*, float*, uint16_t*, int64_t, const int64_t*, const int*, int, const pvr::AdamGroup*,
-                    const pvr::AdamGroup*, int, const float*, int, hipStream_t);
-hipError_t pvr_scale_by_clip(float*, int64_t, const float*, hipStream_t);
-hipError_t pvr_adam_t(float*, const float*, float*, float*, uint16_t*, uint16_t*, const int64_t*, int, int, const int64_t*, int, int64_t,
-                      const pvr::AdamGroup*, const pvr::AdamGroup*, int, const float*, int, hipStream_t);
-hipError_t pvr_fp8_quant(const uint16_t*, int64_t, uint8_t*, int64_t, int64_t, int, const float*, unsigned*, int, hipStream_t);
-hipError_t pvr_fp8_dequant(const uint8_t*, float*, int64_t, const float*, int, hipStream_t);
-hipError_t pvr_fp8_scale_update(float*, int, unsigned*, float*, float*, const float*, int, int, float, hipStream_t);
-hipError_t pvr_fp8_quant_t(const uint16_t*, int64_t, uint8_t*, int64_t, int, int, const float*, int, hipStream_t);
-hipError_t pvr_fp8_transpose(const uint8_t*, int64_t, uint8_t*, int64_t, int, int, hipStream_t);
-hipError_t pvr_fp8_quant_multi(const int64_t*, int, int64_t, const float*, unsigned*, int, int, hipStream_t);
-int pvr_attn_bwd_key_blocks(int);
-int pvr_attn_bwd_needs_dq_acc(int, int, int, int, int);
-int pvr_attn_bwd_waves(int);
-int pvr_attn_bwd_uses_pipe(int, int, int, int, int64_t, int64_t, int64_t, int64_t, int);
-int pvr_attn_bwd_part_rows(int, int, int, int, int64_t, int64_t, int64_t, int64_t, int);
-hipError_t pvr_attn_fwd(const uint16_t*, int64_t, uint16_t*, int64_t, float*, int, int, int, int, float, const uint64_t*, uint64_t,
-                        uint32_t, float, uint8_t*, int64_t, const float*, unsigned*, int, hipStream_t);
-int pvr_attn_dbias_splits(int, int);
-hipError_t pvr_splitk_epilogue(const float*, int, int64_t, int, int, const float*, const uint16_t*, int64_t, int, uint16_t*, int64_t,
-                               hipStream_t);
-hipError_t pvr_attn_dbias_reduce(const float*, float*, float*, int, int, int, int, hipStream_t);
-hipError_t pvr_attn_bwd(const uint16_t*, int64_t, const uint16_t*, int64_t, const uint16_t*, int64_t, const float*, uint16_t*, int64_t, float*, int, float*, float*, float*, int, int, int, int, float,
-                        const uint64_t*, uint64_t, uint32_t, float, uint8_t*, int64_t, const float*, unsigned*,
-                        int, int, hipStream_t);
-int64_t pvr_attn_bwd_ws_floats(int, int, int, int, int, int, int);
-int pvr_attn_bwd_q8_ok(int, int);
-}
+#include "kernels.h"
 
 namespace {
 
@@ -149,6 +70,50 @@ int64_t ld_of(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.stride(0) % 8 == 0 || t.size(0) == 1, name, " leading dimension must be a multiple of 8 elements");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, " must be 16-byte aligned");
   return t.size(0) == 1 ? t.size(1) : t.stride(0);
+}
+
+// The dropout site of every kernel that draws or recomputes a mask (pvr::DropSite): the only place
+// that derives thr and scale from drop_p. drop_p == 0: no dropout (seed unread).
+pvr::DropSite drop_args(const c10::optional<torch::Tensor>& seed, int64_t seed_offset, double drop_p, const char* what) {
+  pvr::DropSite d;
+  d.offset = (uint64_t)seed_offset;
+  if (drop_p > 0.0) {
+    TORCH_CHECK(seed.has_value() && seed->defined() && seed->is_cuda() && seed->scalar_type() == torch::kInt64 && seed->numel() >= 1,
+                what, ": dropout needs an int64 seed tensor on the GPU");
+    d.seed = reinterpret_cast<const uint64_t*>(seed->data_ptr());
+    d.thr = (uint32_t)llround(drop_p * 65536.0);
+    if (d.thr > 65535) d.thr = 65535;
+    d.scale = (float)(65536.0 / (65536.0 - d.thr));
+  }
+  return d;
+}
+// GemmParams keeps the site flat (the GEMM kernels take the struct by value); untouched without dropout
+void set_drop(pvr::GemmParams& p, const pvr::DropSite& d) {
+  if (!d.seed) return;
+  p.seed_ptr = d.seed; p.seed_offset = d.offset; p.drop_thr = d.thr; p.drop_scale = d.scale;
+}
+
+// The optional fp8 copy of a kernel's [rows, cols] output (pvr::Fp8Copy; q_fmt 0 e4m3, 1 e5m2):
+// q_out uint8 with its row stride and base pointer multiples of `align` bytes, q_scale the delayed
+// scale (f32), q_amax the amax record (int32 holding float bits). q_out None: no copy.
+pvr::Fp8Copy fp8_copy(const c10::optional<torch::Tensor>& q_out, const c10::optional<torch::Tensor>& q_scale,
+                      const c10::optional<torch::Tensor>& q_amax, int64_t q_fmt, int64_t rows, int64_t cols, int64_t align,
+                      const char* what) {
+  pvr::Fp8Copy q;
+  q.fmt = (int)q_fmt;
+  if (!q_out.has_value() || !q_out->defined()) return q;
+  TORCH_CHECK(q_out->is_cuda() && q_out->scalar_type() == torch::kUInt8 && q_out->dim() == 2 && q_out->stride(1) == 1 &&
+                  q_out->size(0) >= rows && q_out->size(1) >= cols && q_out->stride(0) % align == 0 &&
+                  reinterpret_cast<uintptr_t>(q_out->data_ptr()) % align == 0,
+              what, ": q_out must be uint8 [>= ", rows, "][>= ", cols, "] with unit column stride, row stride and base multiples of ", align);
+  TORCH_CHECK(q_scale.has_value() && q_scale->defined() && q_amax.has_value() && q_amax->defined() && q_amax->is_cuda() &&
+                  q_amax->scalar_type() == torch::kInt32 && (q_fmt == 0 || q_fmt == 1),
+              what, ": q_out needs q_scale (f32), q_amax (int32 on the GPU) and q_fmt 0 / 1");
+  q.out = q_out->data_ptr<uint8_t>();
+  q.ld = q_out->stride(0);
+  q.scale = f32(*q_scale, "q_scale");
+  q.amax = reinterpret_cast<unsigned*>(q_amax->data_ptr());
+  return q;
 }
 
 // Split-K tail of the one-tile-per-workgroup GEMMs (GemmParams::tail_*): per (device, stream) a
@@ -261,15 +226,7 @@ void gemm(torch::Tensor A, bool a_kcontig, torch::Tensor B, bool b_kcontig, torc
   if (aux.has_value() && aux->defined()) { p.aux = const_cast<uint16_t*>(bf(*aux, "aux")); p.ld_aux = ld_of(*aux, "aux"); }
   if (epi == 2) TORCH_CHECK(p.aux != nullptr, "gemm: the dGELU epilogue needs aux");  // GELU: aux optional (inference)
   p.row_group = (int)row_group; p.row_stride_group = (int)row_stride_group; p.row_offset = (int)row_offset;
-  if (drop_p > 0.0) {
-    TORCH_CHECK(seed.has_value() && seed->defined() && seed->scalar_type() == torch::kInt64, "dropout needs an int64 seed tensor");
-    p.seed_ptr = reinterpret_cast<const uint64_t*>(seed->data_ptr());
-    p.seed_offset = (uint64_t)seed_offset;
-    uint32_t thr = (uint32_t)llround(drop_p * 65536.0);
-    if (thr > 65535) thr = 65535;
-    p.drop_thr = thr;
-    p.drop_scale = (float)(65536.0 / (65536.0 - thr));
-  }
+  set_drop(p, drop_args(seed, seed_offset, drop_p, "gemm"));
   p.k_split_len = k_split > 0 ? (int)(((k_split + 63) / 64) * 64) : (int)(((K + 63) / 64) * 64);
   p.epi = (int)epi;
   p.tile_cfg = (int)tile_cfg;
@@ -325,37 +282,13 @@ std::vector<torch::Tensor> layernorm_fwd_q8(torch::Tensor x, torch::Tensor w, to
   auto mean = torch::empty({rows}, x.options().dtype(torch::kFloat32));
   auto rstd = torch::empty({rows}, x.options().dtype(torch::kFloat32));
   TORCH_CHECK(x.stride(-1) == 1, "layernorm: x last dim must be contiguous");
-  TORCH_CHECK(q_out.is_cuda() && q_out.scalar_type() == torch::kUInt8 && q_out.dim() == 2 && q_out.size(0) >= rows &&
-                  q_out.size(1) >= D && q_out.stride(1) == 1 && q_out.stride(0) % 8 == 0 &&
-                  reinterpret_cast<uintptr_t>(q_out.data_ptr()) % 8 == 0,
-              "layernorm_fwd_q8: q_out uint8 [rows][D], 8-byte aligned rows");
-  TORCH_CHECK(q_amax.is_cuda() && q_amax.scalar_type() == torch::kInt32, "layernorm_fwd_q8: q_amax int32");
+  TORCH_CHECK(q_out.defined(), "layernorm_fwd_q8: q_out is required");
+  const pvr::Fp8Copy q = fp8_copy(q_out, q_scale, q_amax, 0, rows, D, 8, "layernorm_fwd_q8");
   // skip_y: only the e4m3 copy is consumed (the bf16 y stays allocated, unwritten)
-  check(pvr_layernorm_fwd_q8(bf(x, "x"), x_row_stride, f32(w, "w"), f32(b, "b"), skip_y ? nullptr : bf_mut(y, "y"), D,
-                             reinterpret_cast<uint8_t*>(q_out.data_ptr()), q_out.stride(0), f32(q_scale, "q_scale"),
-                             reinterpret_cast<unsigned*>(q_amax.data_ptr<int32_t>()), f32_mut(mean, "mean"), f32_mut(rstd, "rstd"),
-                             (int)rows, (int)D, (float)eps, stream()),
+  check(pvr_layernorm_fwd_q8(bf(x, "x"), x_row_stride, f32(w, "w"), f32(b, "b"), skip_y ? nullptr : bf_mut(y, "y"), D, q,
+                             f32_mut(mean, "mean"), f32_mut(rstd, "rstd"), (int)rows, (int)D, (float)eps, stream()),
         "layernorm_fwd_q8");
   return {y, mean, rstd};
-}
-
-// Dropout parameters shared by every kernel that recomputes a mask: keep iff the element's 16-bit
-// hash >= thr16 = round(p * 65536); kept values scale by 65536 / (65536 - thr16).
-struct DropArgs {
-  const uint64_t* seed = nullptr;
-  uint32_t thr = 0;
-  float scale = 1.f;
-};
-DropArgs drop_args(const c10::optional<torch::Tensor>& seed, double drop_p, const char* what) {
-  DropArgs d;
-  if (drop_p > 0.0) {
-    TORCH_CHECK(seed.has_value() && seed->defined(), what, ": dropout needs a seed");
-    d.seed = reinterpret_cast<const uint64_t*>(seed->data_ptr());
-    d.thr = (uint32_t)llround(drop_p * 65536.0);
-    if (d.thr > 65535) d.thr = 65535;
-    d.scale = (float)(65536.0 / (65536.0 - d.thr));
-  }
-  return d;
 }
 
 // dz (optional, needs drop_p > 0): dropout backward of the layer that produced x's residual stream,
@@ -368,41 +301,28 @@ void layernorm_bwd(torch::Tensor dy, int64_t dy_stride, torch::Tensor x, int64_t
                    c10::optional<torch::Tensor> q_scale, c10::optional<torch::Tensor> q_amax, bool dz_nostore,
                    int64_t q_fmt) {
   const int64_t D = w.numel();
+  pvr::LnBwdParams p{};
+  p.dy = bf(dy, "dy"); p.dy_stride = dy_stride;
+  p.x = bf(x, "x"); p.x_stride = x_stride;
+  p.mean = f32(mean, "mean"); p.rstd = f32(rstd, "rstd"); p.w = f32(w, "w");
+  p.dres = opt_ptr<const uint16_t>(dres); p.dres_stride = dres_stride;
+  p.dx = bf_mut(dx, "dx"); p.dx_stride = dx_stride;
+  p.dw = opt_ptr<float>(dw); p.db = opt_ptr<float>(db); p.dsum = opt_ptr<float>(dsum);
+  const bool has_dz = dz.has_value() && dz->defined();
+  if (has_dz) {
+    TORCH_CHECK(drop_p > 0.0, "layernorm_bwd: dz is the dropout backward, it needs drop_p > 0");
+    p.dz = const_cast<uint16_t*>(bf(*dz, "dz"));
+    p.dz_stride = ld_of(*dz, "dz");
+  }
+  p.drop = drop_args(seed, seed_offset, has_dz ? drop_p : 0.0, "layernorm_bwd");
+  p.dz_nostore = dz_nostore ? 1 : 0;
   // optional e5m2 copy of the last-written gradient (dz if given, else dx) with a delayed scale
   // and an amax record: the producer-side quantization for the next fp8 dgrad GEMM
-  uint8_t* qp = nullptr;
-  int64_t ldq = 0;
-  const float* qs = nullptr;
-  unsigned* qa = nullptr;
-  if (q_out.has_value() && q_out->defined()) {
-    TORCH_CHECK(q_out->is_cuda() && q_out->scalar_type() == torch::kUInt8 && q_out->dim() == 2 && q_out->stride(1) == 1 &&
-                    q_out->size(0) >= rows && q_out->size(1) >= D && q_out->stride(0) % 8 == 0 &&
-                    reinterpret_cast<uintptr_t>(q_out->data_ptr()) % 8 == 0,
-                "layernorm_bwd: q_out uint8 [>= rows][>= D], row stride a multiple of 8, 8-byte aligned");
-    TORCH_CHECK(q_scale.has_value() && q_scale->defined() && q_amax.has_value() && q_amax->defined() &&
-                    q_amax->is_cuda() && q_amax->scalar_type() == torch::kInt32,
-                "layernorm_bwd: q_out needs q_scale (f32) and q_amax (int32)");
-    qp = q_out->data_ptr<uint8_t>();
-    ldq = q_out->stride(0);
-    qs = f32(*q_scale, "q_scale");
-    qa = reinterpret_cast<unsigned*>(q_amax->data_ptr());
-  }
-  uint16_t* dzp = nullptr;
-  int64_t ldz = 0;
-  DropArgs d;
-  if (dz.has_value() && dz->defined()) {
-    TORCH_CHECK(drop_p > 0.0, "layernorm_bwd: dz is the dropout backward, it needs drop_p > 0");
-    dzp = const_cast<uint16_t*>(bf(*dz, "dz"));
-    ldz = ld_of(*dz, "dz");
-    d = drop_args(seed, drop_p, "layernorm_bwd");
-  }
-  check(pvr_layernorm_bwd(bf(dy, "dy"), dy_stride, bf(x, "x"), x_stride, f32(mean, "mean"), f32(rstd, "rstd"), f32(w, "w"),
-                          opt_ptr<const uint16_t>(dres), dres_stride, bf_mut(dx, "dx"), dx_stride, opt_ptr<float>(dw),
-                          opt_ptr<float>(db), opt_ptr<float>(dsum), dzp, ldz, d.seed, (uint64_t)seed_offset, d.thr, d.scale,
-                          dz_nostore ? 1 : 0, qp, ldq, qs, qa, (int)q_fmt, (int)rows, (int)D,
-                          g_deterministic && (opt_ptr<float>(dw) || opt_ptr<float>(db) || opt_ptr<float>(dsum)) ? det_scratch((int64_t)pvr_layernorm_bwd_blocks((int)rows, (int)D) * 3 * D, x.options()) : nullptr,
-                          stream()),
-        "layernorm_bwd");
+  p.q = fp8_copy(q_out, q_scale, q_amax, q_fmt, rows, D, 8, "layernorm_bwd");
+  p.rows = (int)rows; p.D = (int)D;
+  if (g_deterministic && (p.dw || p.db || p.dsum))
+    p.part = det_scratch((int64_t)pvr_layernorm_bwd_blocks((int)rows, (int)D) * 3 * D, x.options());
+  check(pvr_layernorm_bwd(&p, stream()), "layernorm_bwd");
 }
 
 // out (+)= ws.sum(0) for a split-K workspace ws [S, rows, cols] (out: contiguous [rows, cols])
@@ -470,30 +390,13 @@ void transpose_batched(torch::Tensor src, torch::Tensor dst, torch::Tensor meta,
 void colsum(torch::Tensor dy, int64_t rows, int64_t N, c10::optional<torch::Tensor> db, c10::optional<torch::Tensor> dz,
             c10::optional<torch::Tensor> seed, int64_t seed_offset, double drop_p, c10::optional<torch::Tensor> q_out,
             c10::optional<torch::Tensor> q_scale, c10::optional<torch::Tensor> q_amax, int64_t q_fmt) {
-  const DropArgs d = drop_args(seed, drop_p, "colsum");
+  const pvr::DropSite d = drop_args(seed, seed_offset, drop_p, "colsum");
   int64_t ldz = 0;
   uint16_t* dzp = nullptr;
   if (dz.has_value() && dz->defined()) { dzp = const_cast<uint16_t*>(bf(*dz, "dz")); ldz = ld_of(*dz, "dz"); }
   // optional fp8 copy (q_fmt 1 e5m2, 0 e4m3) of the (masked) gradient + amax record (the fp8 dgrad operand)
-  uint8_t* qp = nullptr;
-  int64_t ldq = 0;
-  const float* qs = nullptr;
-  unsigned* qa = nullptr;
-  if (q_out.has_value() && q_out->defined()) {
-    TORCH_CHECK(q_out->is_cuda() && q_out->scalar_type() == torch::kUInt8 && q_out->dim() == 2 && q_out->stride(1) == 1 &&
-                    q_out->size(0) >= rows && q_out->size(1) >= N && q_out->stride(0) % 8 == 0 &&
-                    reinterpret_cast<uintptr_t>(q_out->data_ptr()) % 8 == 0,
-                "colsum: q_out uint8 [>= rows][>= N], row stride a multiple of 8, 8-byte aligned");
-    TORCH_CHECK(q_scale.has_value() && q_scale->defined() && q_amax.has_value() && q_amax->defined() && q_amax->is_cuda() &&
-                    q_amax->scalar_type() == torch::kInt32,
-                "colsum: q_out needs q_scale (f32) and q_amax (int32)");
-    qp = q_out->data_ptr<uint8_t>();
-    ldq = q_out->stride(0);
-    qs = f32(*q_scale, "q_scale");
-    qa = reinterpret_cast<unsigned*>(q_amax->data_ptr());
-  }
-  check(pvr_colsum(bf(dy, "dy"), ld_of(dy, "dy"), (int)rows, (int)N, opt_ptr<float>(db), dzp, ldz, d.seed, (uint64_t)seed_offset,
-                   d.thr, d.scale, qp, ldq, qs, qa, (int)q_fmt,
+  const pvr::Fp8Copy q = fp8_copy(q_out, q_scale, q_amax, q_fmt, rows, N, 8, "colsum");
+  check(pvr_colsum(bf(dy, "dy"), ld_of(dy, "dy"), (int)rows, (int)N, opt_ptr<float>(db), dzp, ldz, d, q,
                    g_deterministic && opt_ptr<float>(db) ? det_scratch((int64_t)pvr_colsum_part_rows((int)rows) * N, dy.options()) : nullptr, stream()),
         "colsum");
 }
@@ -555,36 +458,19 @@ int64_t im2col_u8(torch::Tensor img, torch::Tensor out, std::vector<double> mean
 
 void cls_rows(torch::Tensor cls, torch::Tensor pos, torch::Tensor out, int64_t B, int64_t D, int64_t row_stride,
               c10::optional<torch::Tensor> seed, int64_t seed_offset, double drop_p) {
-  uint32_t thr = 0;
-  float scale = 1.f;
-  const uint64_t* sp = nullptr;
-  if (drop_p > 0.0) {
-    sp = reinterpret_cast<const uint64_t*>(seed->data_ptr());
-    thr = (uint32_t)llround(drop_p * 65536.0);
-    if (thr > 65535) thr = 65535;
-    scale = (float)(65536.0 / (65536.0 - thr));
-  }
-  check(pvr_cls_rows(f32(cls, "cls"), f32(pos, "pos"), bf_mut(out, "out"), (int)B, (int)D, row_stride, sp, (uint64_t)seed_offset,
-                     thr, scale, stream()),
+  check(pvr_cls_rows(f32(cls, "cls"), f32(pos, "pos"), bf_mut(out, "out"), (int)B, (int)D, row_stride,
+                     drop_args(seed, seed_offset, drop_p, "cls_rows"), stream()),
         "cls_rows");
 }
 
 void patch_bwd(torch::Tensor dE, int64_t B, int64_t ntok, int64_t D, c10::optional<torch::Tensor> dpos, c10::optional<torch::Tensor> dcls,
                c10::optional<torch::Tensor> dconv, c10::optional<torch::Tensor> dbias, c10::optional<torch::Tensor> seed,
                int64_t seed_offset, double drop_p) {
-  uint32_t thr = 0;
-  float scale = 1.f;
-  const uint64_t* sp = nullptr;
-  if (drop_p > 0.0) {
-    sp = reinterpret_cast<const uint64_t*>(seed->data_ptr());
-    thr = (uint32_t)llround(drop_p * 65536.0);
-    if (thr > 65535) thr = 65535;
-    scale = (float)(65536.0 / (65536.0 - thr));
-  }
+  const pvr::DropSite d = drop_args(seed, seed_offset, drop_p, "patch_bwd");
   TORCH_CHECK(dE.numel() == B * ntok * D, "patch_bwd: dE must hold B * ntok * D elements");
   auto ws = torch::empty({pvr_patch_bwd_ws_floats((int)B, (int)ntok, (int)D)}, dE.options().dtype(torch::kFloat32));
   check(pvr_patch_bwd(bf(dE, "dE"), (int)B, (int)ntok, (int)D, ws.data_ptr<float>(), opt_ptr<float>(dpos), opt_ptr<float>(dcls), opt_ptr<uint16_t>(dconv),
-                      opt_ptr<float>(dbias), sp, (uint64_t)seed_offset, thr, scale, stream()),
+                      opt_ptr<float>(dbias), d, stream()),
         "patch_bwd");
 }
 
@@ -615,7 +501,7 @@ void grad_norm(torch::Tensor g, double max_norm, torch::Tensor workspace, torch:
   check(pvr_grad_norm(f32(g, "g"), g.numel(), (float)max_norm, f32_mut(workspace, "ws"), f32_mut(out, "out"), stream()), "grad_norm");
 }
 
-// Param-group table float32 [G][8] (csrc/optim.hip AdamGroup): a CUDA tensor is read by the kernel
+// Param-group table float32 [G][8] (kernels.h AdamGroup): a CUDA tensor is read by the kernel
 // (graph-captured steps); a CPU tensor is copied into the launch's kernel arguments (G <= 8), so an
 // eager step needs no host-to-device copy of its per-step lr / bias corrections.
 struct GroupTable {
@@ -790,30 +676,12 @@ void gemm_fp8(torch::Tensor A, int64_t fmt_a, torch::Tensor B, int64_t fmt_b, to
     // fp8 copy of the GELU / dGELU output from the register-direct epilogue (its preconditions:
     // 16-B column groups, 31-bit offsets of every row-major operand it touches)
     TORCH_CHECK(epi == 1 || epi == 2, "gemm_fp8: q_out with the GELU / dGELU epilogues only");
-    TORCH_CHECK(q_out->is_cuda() && q_out->scalar_type() == torch::kUInt8 && q_out->dim() == 2 && q_out->stride(1) == 1 &&
-                    q_out->size(0) >= M && q_out->size(1) >= N && q_out->stride(0) % 8 == 0 &&
-                    reinterpret_cast<uintptr_t>(q_out->data_ptr()) % 8 == 0,
-                "gemm_fp8: q_out uint8 [M][N], row stride and base 8-byte aligned");
-    TORCH_CHECK(q_scale.has_value() && q_scale->defined() && q_amax.has_value() && q_amax->defined() &&
-                    q_amax->scalar_type() == torch::kInt32 && q_amax->is_cuda() && (q_fmt == 0 || q_fmt == 1),
-                "gemm_fp8: q_out needs q_scale (f32), q_amax (int32) and q_fmt 0 / 1");
+    const pvr::Fp8Copy q = fp8_copy(q_out, q_scale, q_amax, q_fmt, M, N, 8, "gemm_fp8");
     const int64_t ld_max = std::max(std::max(p.ldc, p.ld_aux), std::max(p.ld_resid, (int64_t)N));
     TORCH_CHECK(M * ld_max * 2 < (1ll << 31), "gemm_fp8: q_out path needs 31-bit output offsets");
-    p.q_out = reinterpret_cast<uint8_t*>(q_out->data_ptr());
-    p.ld_q = q_out->stride(0);
-    p.q_scale = f32(*q_scale, "q_scale");
-    p.q_amax = reinterpret_cast<unsigned*>(q_amax->data_ptr<int32_t>());
-    p.q_fmt = (int)q_fmt;
+    p.q_out = q.out; p.ld_q = q.ld; p.q_scale = q.scale; p.q_amax = q.amax; p.q_fmt = q.fmt;
   }
-  if (drop_p > 0.0) {
-    TORCH_CHECK(seed.has_value() && seed->defined() && seed->scalar_type() == torch::kInt64, "dropout needs an int64 seed tensor");
-    p.seed_ptr = reinterpret_cast<const uint64_t*>(seed->data_ptr());
-    p.seed_offset = (uint64_t)seed_offset;
-    uint32_t thr = (uint32_t)llround(drop_p * 65536.0);
-    if (thr > 65535) thr = 65535;
-    p.drop_thr = thr;
-    p.drop_scale = (float)(65536.0 / (65536.0 - thr));
-  }
+  set_drop(p, drop_args(seed, seed_offset, drop_p, "gemm_fp8"));
   p.k_split_len = (int)K;
   p.epi = (int)epi;
   p.tile_cfg = 12;
@@ -968,27 +836,11 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor qkv, int64_t B, int64_t N, int
   auto lse = torch::empty({B * H, N}, qkv.options().dtype(torch::kFloat32));
   TORCH_CHECK(!q_only || (q_out.has_value() && q_out->defined()), "attn_fwd: q_only needs q_out");
   TORCH_CHECK(qkv.size(0) == B * N, "attn_fwd: qkv rows != B*N");
-  const DropArgs d = drop_args(seed, drop_p, "attn_fwd");
-  uint8_t* q8 = nullptr;
-  int64_t q8_ld = 0;
-  const float* q8_qs = nullptr;
-  unsigned* q8_amax = nullptr;
-  if (q_out.has_value() && q_out->defined()) {
-    // e4m3 copy of the output (producer-side quantization for an fp8 out-proj GEMM)
-    TORCH_CHECK(q_out->is_cuda() && q_out->scalar_type() == torch::kUInt8 && q_out->dim() == 2 && q_out->size(0) >= B * N &&
-                    q_out->size(1) >= D && q_out->stride(1) == 1 && q_out->stride(0) % 4 == 0,
-                "attn_fwd: q_out uint8 [B*N][D]");
-    TORCH_CHECK(q_scale.has_value() && q_scale->defined() && q_amax.has_value() && q_amax->defined() &&
-                    q_amax->scalar_type() == torch::kInt32,
-                "attn_fwd: q_out needs q_scale (f32) and q_amax (int32)");
-    q8 = reinterpret_cast<uint8_t*>(q_out->data_ptr());
-    q8_ld = q_out->stride(0);
-    q8_qs = f32(*q_scale, "q_scale");
-    q8_amax = reinterpret_cast<unsigned*>(q_amax->data_ptr<int32_t>());
-  }
+  const pvr::DropSite d = drop_args(seed, seed_offset, drop_p, "attn_fwd");
+  // e4m3 copy of the output (producer-side quantization for an fp8 out-proj GEMM)
+  const pvr::Fp8Copy q8 = fp8_copy(q_out, q_scale, q_amax, 0, B * N, D, 4, "attn_fwd");
   check(pvr_attn_fwd(bf(qkv, "qkv"), ld_of(qkv, "qkv"), bf_mut(out, "out"), D, f32_mut(lse, "lse"), (int)B, (int)N, (int)H, (int)D,
-                     (float)scale, d.seed, (uint64_t)seed_offset, d.thr, d.scale, q8, q8_ld, q8_qs, q8_amax, q_only ? 1 : 0,
-                     stream()),
+                     (float)scale, d, q8, q_only ? 1 : 0, stream()),
         "attn_fwd");
   return {out, lse};
 }
@@ -1069,7 +921,7 @@ torch::Tensor attn_bwd(torch::Tensor dout, torch::Tensor qkv, torch::Tensor out,
   auto dqkv = torch::empty_like(qkv);
   torch::Tensor dq_acc;
   int dq_rezero = 0;
-  const DropArgs drop = drop_args(seed, drop_p, "attn_bwd");
+  const pvr::DropSite drop = drop_args(seed, seed_offset, drop_p, "attn_bwd");
   const int has_drop = drop.seed ? 1 : 0;
   const int64_t dh = D / H;
   // fused in_proj bias gradient: per-(batch, head, row) partials written by the kernels (no atomics;
@@ -1104,35 +956,25 @@ torch::Tensor attn_bwd(torch::Tensor dout, torch::Tensor qkv, torch::Tensor out,
     if (!dq_acc.defined()) dq_acc = torch::zeros({B * N, D}, qkv.options().dtype(torch::kFloat32));
   }
   // optional e5m2 copy of dQKV + amax record (the fp8 recipe's dgrad / weight-gradient operand)
-  uint8_t* qp = nullptr;
-  int64_t ldq = 0;
-  const float* qs = nullptr;
-  unsigned* qa = nullptr;
-  if (q_out.has_value() && q_out->defined()) {
+  const pvr::Fp8Copy q8 = fp8_copy(q_out, q_scale, q_amax, q_fmt, B * N, 3 * D, 4, "attn_bwd");
+  if (q8.out)
     TORCH_CHECK(pvr_attn_bwd_q8_ok((int)N, has_drop) && !old_db && !pipe, "attn_bwd: no e5m2 dQKV copy for this shape (see attn_bwd_q8_ok)");
-    TORCH_CHECK(q_out->is_cuda() && q_out->scalar_type() == torch::kUInt8 && q_out->dim() == 2 && q_out->stride(1) == 1 &&
-                    q_out->size(0) >= B * N && q_out->size(1) >= 3 * D && q_out->stride(0) % 4 == 0 &&
-                    reinterpret_cast<uintptr_t>(q_out->data_ptr()) % 4 == 0,
-                "attn_bwd: q_out uint8 [B*N][>= 3D], row stride a multiple of 4");
-    TORCH_CHECK(q_scale.has_value() && q_scale->defined() && q_amax.has_value() && q_amax->defined() && q_amax->is_cuda() &&
-                    q_amax->scalar_type() == torch::kInt32,
-                "attn_bwd: q_out needs q_scale (f32) and q_amax (int32)");
-    qp = q_out->data_ptr<uint8_t>();
-    ldq = q_out->stride(0);
-    qs = f32(*q_scale, "q_scale");
-    qa = reinterpret_cast<unsigned*>(q_amax->data_ptr());
-  }
-  float* dbias_arg = pipe && dbias_part.defined() ? dbias_part.data_ptr<float>() : old_db ? old_part.data_ptr<float>() : nullptr;
-  float* bpart_arg = !pipe && dbias_part.defined() ? dbias_part.data_ptr<float>() : nullptr;
   // pre-pass outputs of the generic backward (per-query delta, lastkey path: ds_last; slab path: dQ
   // slabs): a persistent per-(device, stream) scratch, so the slab path (~0.9 GB per ViT-L/16@384
   // b128 layer) is not allocated on every backward
   auto ws = attn_scratch(pvr_attn_bwd_ws_floats((int)B, (int)N, (int)H, (int)D, old_db, has_drop, g_deterministic ? 1 : 0), qkv.options());
-  const hipError_t err = pvr_attn_bwd(bf(qkv, "qkv"), lds[0], bf(out, "out"), lds[2], bf(dout, "dout"), lds[1], f32(lse, "lse"),
-                                      bf_mut(dqkv, "dqkv"), lds[3], dq_acc.defined() ? dq_acc.data_ptr<float>() : nullptr, dq_rezero,
-                                      dbias_arg, bpart_arg, ws.data_ptr<float>(), (int)B, (int)N, (int)H, (int)D, (float)scale,
-                                      drop.seed, (uint64_t)seed_offset, drop.thr, drop.scale, qp, ldq, qs, qa, q_only && qp ? 1 : 0,
-                                      (int)q_fmt, stream());
+  pvr::AttnBwdParams p{};
+  p.qkv = bf(qkv, "qkv"); p.ld = lds[0];
+  p.out = bf(out, "out"); p.ld_o = lds[2];
+  p.dout = bf(dout, "dout"); p.ld_do = lds[1];
+  p.dqkv = bf_mut(dqkv, "dqkv"); p.ld_dq = lds[3];
+  p.lse = f32(lse, "lse"); p.ws = ws.data_ptr<float>();
+  p.dq_acc = dq_acc.defined() ? dq_acc.data_ptr<float>() : nullptr; p.dq_rezero = dq_rezero;
+  p.dbias = pipe && dbias_part.defined() ? dbias_part.data_ptr<float>() : old_db ? old_part.data_ptr<float>() : nullptr;
+  p.bpart = !pipe && dbias_part.defined() ? dbias_part.data_ptr<float>() : nullptr;
+  p.B = (int)B; p.N = (int)N; p.H = (int)H; p.D = (int)D; p.scale = (float)scale;
+  p.drop = drop; p.q8 = q8; p.q8_only = q_only && q8.out ? 1 : 0;
+  const hipError_t err = pvr_attn_bwd(&p, stream());
   // a persistent accumulator is re-zeroed only by a completed backward: after a failed launch it
   // may hold stale partial sums, so it is dropped (re-created zeroed by the next call)
   if (err != hipSuccess && dq_rezero) dq_workspace(0, qkv.options(), true);

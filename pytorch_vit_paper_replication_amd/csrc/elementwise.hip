@@ -4,6 +4,7 @@
 //   * patch embedding: im2col gather (fp32 image -> bf16 patch rows), CLS rows, and the backward
 //     reduction of the embedding-dropout / position-embedding / CLS gradients.
 #include "common.h"
+#include "kernels.h"
 
 namespace pvr {
 namespace {
@@ -551,7 +552,6 @@ extern "C" hipError_t pvr_pad_cols_bf16(const uint16_t* src, int rows, int cols,
   return hipGetLastError();
 }
 
-// meta: int64 [nmat][5] = {src_off, dst_off, rows, cols, tile_prefix}; total_tiles = sum of tiles
 extern "C" hipError_t pvr_transpose_batched(const uint16_t* src, uint16_t* dst, const int64_t* meta, int nmat, int total_tiles,
                                             hipStream_t s) {
   using namespace pvr;
@@ -570,25 +570,22 @@ extern "C" hipError_t pvr_cast_f32_bf16(const float* in, uint16_t* out, int64_t 
   return hipGetLastError();
 }
 
-// row groups of the column-sum kernel's grid (= the partial rows of its deterministic mode)
 extern "C" int pvr_colsum_part_rows(int rows) {
   const int gy = (rows + 63) / 64;
   return gy > 256 ? 256 : gy;
 }
-extern "C" hipError_t pvr_rows_reduce(const float* part, int R, int C, int seg, float* d0, float* d1, float* d2, hipStream_t s);
 
 extern "C" hipError_t pvr_colsum(const uint16_t* dy, int64_t ld, int rows, int N, float* db, uint16_t* dz, int64_t ld_dz,
-                                 const uint64_t* seed_ptr, uint64_t seed_off, uint32_t thr, float scale, uint8_t* q, int64_t ld_q,
-                                 const float* qscale, unsigned* amax, int qfmt, float* part, hipStream_t s) {
+                                 pvr::DropSite drop, pvr::Fp8Copy q, float* part, hipStream_t s) {
   using namespace pvr;
   if (rows <= 0) return hipSuccess;
-  if (N % 8 != 0 || (qfmt != 0 && qfmt != 1)) return hipErrorInvalidValue;
-  if (q && (!qscale || !amax || ld_q % 8 != 0 || reinterpret_cast<uintptr_t>(q) % 8 != 0)) return hipErrorInvalidValue;
+  if (N % 8 != 0 || (q.fmt != 0 && q.fmt != 1)) return hipErrorInvalidValue;
+  if (q.out && (!q.scale || !q.amax || q.ld % 8 != 0 || reinterpret_cast<uintptr_t>(q.out) % 8 != 0)) return hipErrorInvalidValue;
   const int gx = (N / 8 + 63) / 64;
   const int gy = pvr_colsum_part_rows(rows);
   if (!db) part = nullptr;
-  hipLaunchKernelGGL(q ? colsum_kernel<true> : colsum_kernel<false>, dim3(gx, gy), dim3(256), 0, s, dy, ld, rows, N, db, dz, ld_dz,
-                     seed_ptr, seed_off, thr, scale, q, ld_q, qscale, amax, qfmt, part);
+  hipLaunchKernelGGL(q.out ? colsum_kernel<true> : colsum_kernel<false>, dim3(gx, gy), dim3(256), 0, s, dy, ld, rows, N, db, dz, ld_dz,
+                     drop.seed, drop.offset, drop.thr, drop.scale, q.out, q.ld, q.scale, q.amax, q.fmt, part);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || !part) return e;
   return pvr_rows_reduce(part, gy, N, N, db, nullptr, nullptr, s);
@@ -605,8 +602,6 @@ extern "C" hipError_t pvr_im2col(const float* img, uint16_t* out, int B, int C, 
   return hipGetLastError();
 }
 
-// strides in elements (= bytes); geom null: Hs == H and Ws == W. `vec`: the caller has checked the
-// 8-byte load conditions on the base pointer and strides (bindings.cpp im2col_u8).
 extern "C" hipError_t pvr_im2col_u8(const uint8_t* img, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float* mean,
                                     const float* stdv, const float* geom, uint16_t* out, int B, int C, int Hs, int Ws, int H,
                                     int W, int P, int Kp, int vec, hipStream_t s) {
@@ -630,24 +625,23 @@ extern "C" hipError_t pvr_im2col_u8(const uint8_t* img, int64_t sb, int64_t sc, 
 }
 
 extern "C" hipError_t pvr_cls_rows(const float* cls, const float* pos, uint16_t* out, int B, int D, int64_t row_stride,
-                                   const uint64_t* seed_ptr, uint64_t seed_off, uint32_t thr, float scale, hipStream_t s) {
+                                   pvr::DropSite drop, hipStream_t s) {
   using namespace pvr;
   if (B * D <= 0) return hipSuccess;
   int blocks = (B * D + 255) / 256;
   if (blocks > 1024) blocks = 1024;
-  hipLaunchKernelGGL(cls_rows_kernel, dim3(blocks), dim3(256), 0, s, cls, pos, out, B, D, row_stride, seed_ptr, seed_off, thr, scale, (int64_t)0);
+  hipLaunchKernelGGL(cls_rows_kernel, dim3(blocks), dim3(256), 0, s, cls, pos, out, B, D, row_stride, drop.seed, drop.offset, drop.thr, drop.scale, (int64_t)0);
   return hipGetLastError();
 }
 
 extern "C" hipError_t pvr_patch_bwd(const uint16_t* dE, int B, int ntok, int D, float* ws, float* dpos, float* dcls,
-                                    uint16_t* dconv, float* dbias, const uint64_t* seed_ptr, uint64_t seed_off, uint32_t thr,
-                                    float scale, hipStream_t s) {
+                                    uint16_t* dconv, float* dbias, pvr::DropSite drop, hipStream_t s) {
   using namespace pvr;
   if (ntok * D <= 0 || B <= 0) return hipSuccess;
   if (D % 8) return hipErrorInvalidValue;
   const int G = (B + PB_BAT - 1) / PB_BAT;  // ws holds G * ntok * D floats (host-checked)
   hipLaunchKernelGGL(patch_bwd_kernel, dim3((ntok * (D / 8) + 255) / 256, G), dim3(256), 0, s, dE, B, ntok, D, ws, dconv,
-                     seed_ptr, seed_off, thr, scale);
+                     drop.seed, drop.offset, drop.thr, drop.scale);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   // ws also holds the conv-bias partials of the reduction's token blocks, after the group sums
@@ -663,14 +657,13 @@ extern "C" hipError_t pvr_patch_bwd(const uint16_t* dE, int B, int ntok, int D, 
 
 extern "C" int pvr_patch_bwd_groups(int B) { return (B + pvr::PB_BAT - 1) / pvr::PB_BAT; }
 
-// d0/d1/d2[c % seg] += sum over the R rows of part[R][C] (row order: deterministic)
 extern "C" hipError_t pvr_rows_reduce(const float* part, int R, int C, int seg, float* d0, float* d1, float* d2, hipStream_t s) {
   if (R <= 0 || C <= 0) return hipSuccess;
   if (seg <= 0 || C > 3 * seg) return hipErrorInvalidValue;
   hipLaunchKernelGGL(pvr::rows_reduce_kernel, dim3((C + 31) / 32), dim3(256), 0, s, part, R, C, seg, d0, d1, d2);
   return hipGetLastError();
 }
-// floats of the scratch pvr_patch_bwd needs: the group sums and the conv-bias partials
+
 extern "C" int64_t pvr_patch_bwd_ws_floats(int B, int ntok, int D) {
   return ((int64_t)pvr_patch_bwd_groups(B) * ntok + (ntok + pvr::PR_TOK - 1) / pvr::PR_TOK) * D;
 }

@@ -9,6 +9,7 @@
 //           dscale = 1 / qscale (the GEMM epilogue's dequant factor), reset amax; a non-finite
 //           amax is dropped (scales unchanged), so one overflowing step cannot poison the history
 #include "common.h"
+#include "kernels.h"
 
 #include <cstdlib>
 

@@ -18,7 +18,7 @@
 // ds_read_b64_tr_b16 hardware transpose for mn-contig). Two LDS stages: the DMA for tile t+1 is in
 // flight while the MFMAs of tile t run.
 #include "common.h"
-#include "gemm_params.h"
+#include "kernels.h"
 #include <type_traits>
 
 namespace pvr {
@@ -2061,7 +2061,6 @@ hipError_t launch_tile(const GemmParams& p, hipStream_t s) {
 
 }  // namespace pvr
 
-// The split-K tail plan a one-tile-per-workgroup GEMM of this shape gets (0: none): tests / tools.
 extern "C" int pvr_gemm_tail_split(int M, int N, int K, int elem_bytes, int max_units) {
   pvr::GemmParams q{};
   q.K = K;
@@ -2080,13 +2079,8 @@ extern "C" int pvr_gemm_tail_split(int M, int N, int K, int elem_bytes, int max_
 static int g_fp8_persistent = 1;
 extern "C" void pvr_set_fp8_persistent(int mode) { g_fp8_persistent = mode ? 1 : 0; }
 
-extern "C" int pvr_gemm_ws_ok(const pvr::GemmParams* pp, int cus);
-extern "C" hipError_t pvr_gemm_ws(const pvr::GemmParams* pp, int cus, hipStream_t s);
-
-// 1 if tile config 15 (the wave-specialized kernel, gemm_ws.hip) runs this GEMM as given
 extern "C" int pvr_gemm_ws_takes(const pvr::GemmParams* pp) { return pvr_gemm_ws_ok(pp, pvr::device_cus()); }
 
-// Host entry. Returns hipSuccess, or hipErrorInvalidValue for an unsupported layout/epilogue pair.
 extern "C" hipError_t pvr_gemm(const pvr::GemmParams* pp, hipStream_t s) {
   using namespace pvr;
   const GemmParams& p = *pp;

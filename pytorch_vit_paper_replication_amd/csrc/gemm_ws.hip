@@ -32,7 +32,7 @@
 // hand-off stays fp32 (two rounds), so the bias-gradient column sums keep the fp32 accumulator.
 // Reference: /root/reference/models/vit.py:118-126 (MLP block), :166-169; SURVEY.md K9, K10, K11.
 #include "common.h"
-#include "gemm_params.h"
+#include "kernels.h"
 #include <type_traits>
 
 namespace pvr {
@@ -572,9 +572,6 @@ hipError_t launch_ws(const GemmParams& p, hipStream_t s, int cus) {
 }  // namespace
 }  // namespace pvr
 
-// 1 if the wave-specialized kernel takes this GEMM (k-contiguous bf16 operands, bf16-output
-// epilogue without row remap / addend / fp8 copy, K a multiple of 64 and >= 256, 32-bit element
-// indices, 31-bit buffer offsets)
 extern "C" int pvr_gemm_ws_ok(const pvr::GemmParams* pp, int cus) {
   (void)cus;
   const pvr::GemmParams& p = *pp;

@@ -9,6 +9,7 @@
 // from L2 (LDS only for the split-k reduction). They replace
 // torch's F.linear / addmm / sum / copy launches (hipBLASLt Cijk kernels + ATen elementwise).
 #include "common.h"
+#include "kernels.h"
 
 namespace pvr {
 namespace {
@@ -325,8 +326,6 @@ extern "C" hipError_t pvr_head_fwd(const uint16_t* tok, int64_t ld_tok, int B, i
   hipLaunchKernelGGL(head_logits_kernel, dim3(tiles), dim3(256), 0, s, xhat, gamma, beta, W, bias, B, C, D, logits);
   return hipGetLastError();
 }
-
-extern "C" hipError_t pvr_rows_reduce(const float* part, int R, int C, int seg, float* d0, float* d1, float* d2, hipStream_t s);
 
 extern "C" hipError_t pvr_head_bwd(const float* dl, const float* xhat, const float* rstd, const float* gamma, const float* beta,
                                    const float* W, int B, int C, int D, int ntok, float* dW, float* db, float* dgamma, float* dbeta,

@@ -1,0 +1,218 @@
+// The host-kernel interface: every extern "C" launcher (pvr_*) that the csrc/*.hip files define and
+// bindings.cpp calls, declared once. Both sides include this header (hipcc and the host compiler),
+// so a definition that drifts from its declaration no longer compiles (C linkage has no overloads).
+// Plain C++: the HIP runtime API types only, no device code.
+#pragma once
+#include <stdint.h>
+
+#include <hip/hip_runtime_api.h>
+
+#include "gemm_params.h"
+
+namespace pvr {
+
+// One row of the optimizer's param-group table, float32 [G][8] (optim/adam.py _group_array; the
+// last word holds an int)
+struct AdamGroup {
+  float lr, beta1, beta2, eps, weight_decay;
+  float bc1, bc2_sqrt;  // 1 - beta1^t, sqrt(1 - beta2^t)
+  int decoupled;
+};
+static_assert(sizeof(AdamGroup) == 8 * sizeof(float), "AdamGroup is one float32 [8] row of the group table");
+
+// A dropout site: the element's 16-bit hash of (*seed + offset) is kept iff >= thr = round(p * 65536);
+// kept values scale by 65536 / (65536 - thr). seed null: no dropout.
+struct DropSite {
+  const uint64_t* seed = nullptr; uint64_t offset = 0; uint32_t thr = 0; float scale = 1.f;
+};
+
+// Optional fp8 copy of a kernel's output (producer-side quantization of the delayed-scaling recipe):
+// out[r][c] = fp8(v * (*scale)) (fmt 0 e4m3, 1 e5m2; row stride ld bytes), *amax = max(*amax, max|v|)
+// (float bits). out null: none.
+struct Fp8Copy {
+  uint8_t* out = nullptr; int64_t ld = 0; const float* scale = nullptr; unsigned* amax = nullptr; int fmt = 0;
+};
+
+// pvr_layernorm_bwd: dx = dres + LN'(dy); dw / db / dsum (each optional) accumulate dgamma, dbeta
+// and the column sums of dx.
+struct LnBwdParams {
+  const uint16_t* dy; int64_t dy_stride;
+  const uint16_t* x; int64_t x_stride;
+  const float* mean; const float* rstd; const float* w;
+  const uint16_t* dres; int64_t dres_stride;  // optional
+  uint16_t* dx; int64_t dx_stride;
+  float* dw; float* db; float* dsum;
+  // dz (optional, needs drop.seed): dz = mask * scale * dx, the dropout backward of the layer that
+  // produced x's residual stream; dsum then receives dz's column sums. dz_nostore: only dz's fp8
+  // copy is written (needs q.out).
+  uint16_t* dz; int64_t dz_stride; DropSite drop; int dz_nostore;
+  Fp8Copy q;  // copy of the last-written gradient (dz if given, else dx); row stride and base % 8
+  int rows, D;
+  float* part;  // deterministic mode: [pvr_layernorm_bwd_blocks][3][D] partial rows (null: atomics)
+};
+
+// pvr_attn_bwd. dq_acc: f32 [B*N][D] zero-initialised workspace, required iff N > 256 (several key
+// blocks per head); dq_rezero = 1 leaves it zeroed again afterwards (a persistent workspace reused
+// across calls).
+// dbias: optional f32 [B * nkb][3D] partial column sums of dQ | dK | dV (nkb = pvr_attn_bwd_key_blocks;
+// every element is written), whose row sum is the in_proj bias gradient; on the pipelined path
+// (pvr_attn_bwd_uses_pipe) the per-block partials described there.
+// ws: f32 scratch of pvr_attn_bwd_ws_floats floats (the generic path's pre-pass outputs).
+struct AttnBwdParams {
+  const uint16_t* qkv; int64_t ld;
+  const uint16_t* out; int64_t ld_o;
+  const uint16_t* dout; int64_t ld_do;
+  const float* lse;
+  uint16_t* dqkv; int64_t ld_dq;
+  float* dq_acc; int dq_rezero;
+  float* dbias; float* bpart;  // bpart: see pvr_attn_bwd_part_rows
+  float* ws;
+  int B, N, H, D;
+  float scale;
+  DropSite drop;  // the forward's attention-probability dropout
+  Fp8Copy q8;     // copy of dQKV (row stride and base % 4); q8_only: the bf16 dQKV is not stored
+  int q8_only;
+};
+
+}  // namespace pvr
+
+extern "C" {
+
+// ---- gemm.hip, gemm_ws.hip
+// Host entry. Returns hipSuccess, or hipErrorInvalidValue for an unsupported layout/epilogue pair.
+hipError_t pvr_gemm(const pvr::GemmParams* p, hipStream_t s);
+// The split-K tail plan a one-tile-per-workgroup GEMM of this shape gets (0: none): tests / tools.
+int pvr_gemm_tail_split(int M, int N, int K, int elem_bytes, int max_units);
+void pvr_set_fp8_persistent(int mode);
+// 1 if the wave-specialized kernel takes this GEMM (k-contiguous bf16 operands, bf16-output
+// epilogue without row remap / addend / fp8 copy, K a multiple of 64 and >= 256, 32-bit element
+// indices, 31-bit buffer offsets)
+int pvr_gemm_ws_ok(const pvr::GemmParams* p, int cus);
+hipError_t pvr_gemm_ws(const pvr::GemmParams* p, int cus, hipStream_t s);
+// 1 if tile config 15 (the wave-specialized kernel, gemm_ws.hip) runs this GEMM as given
+int pvr_gemm_ws_takes(const pvr::GemmParams* p);
+
+// ---- layernorm.hip
+hipError_t pvr_layernorm_fwd(const uint16_t* x, int64_t x_stride, const float* w, const float* b, uint16_t* y, int64_t y_stride,
+                             float* mean, float* rstd, int rows, int D, float eps, hipStream_t s);
+void pvr_set_ln_fwd_q8_grid(int per_cu);
+// pvr_layernorm_fwd plus the e4m3 copy q (row stride a multiple of 8) with the amax record (see
+// ln_fwd_q8_kernel); y null: only the copy is written
+hipError_t pvr_layernorm_fwd_q8(const uint16_t* x, int64_t x_stride, const float* w, const float* b, uint16_t* y, int64_t y_stride,
+                                pvr::Fp8Copy q, float* mean, float* rstd, int rows, int D, float eps, hipStream_t s);
+// grid of the LayerNorm backward (= the partial rows [blocks][3][D] of its deterministic mode)
+int pvr_layernorm_bwd_blocks(int rows, int D);
+hipError_t pvr_layernorm_bwd(const pvr::LnBwdParams* p, hipStream_t s);
+
+// ---- elementwise.hip
+hipError_t pvr_cast_f32_bf16(const float* in, uint16_t* out, int64_t n, hipStream_t s);
+hipError_t pvr_splitk_reduce(const float* ws, int S, int64_t stride, float* out, int64_t n, int ocols, int wcols, int accumulate,
+                             hipStream_t s);
+hipError_t pvr_splitk_epilogue(const float* ws, int S, int64_t stride, int M, int N, const float* bias, const uint16_t* resid,
+                               int64_t ld_resid, int gelu, uint16_t* out, int64_t ldc, hipStream_t s);
+hipError_t pvr_pad_cols_bf16(const uint16_t* src, int rows, int cols, uint16_t* dst, int ld_dst, hipStream_t s);
+// meta: int64 [nmat][5] = {src_off, dst_off, rows, cols, tile_prefix}; total_tiles = sum of tiles
+hipError_t pvr_transpose_batched(const uint16_t* src, uint16_t* dst, const int64_t* meta, int nmat, int total_tiles, hipStream_t s);
+// row groups of the column-sum kernel's grid (= the partial rows of its deterministic mode)
+int pvr_colsum_part_rows(int rows);
+// db (optional) += column sums of dy, or of dz = mask * scale * dy when drop.seed is set; dz
+// (optional) receives that product, q its fp8 copy (row stride and base % 8); part: deterministic
+// mode scratch [pvr_colsum_part_rows][N]
+hipError_t pvr_colsum(const uint16_t* dy, int64_t ld, int rows, int N, float* db, uint16_t* dz, int64_t ld_dz, pvr::DropSite drop,
+                      pvr::Fp8Copy q, float* part, hipStream_t s);
+// d0/d1/d2[c % seg] += sum over the R rows of part[R][C] (row order: deterministic)
+hipError_t pvr_rows_reduce(const float* part, int R, int C, int seg, float* d0, float* d1, float* d2, hipStream_t s);
+hipError_t pvr_im2col(const float* img, uint16_t* out, int B, int C, int H, int W, int P, int Kp, hipStream_t s);
+// strides in elements (= bytes); geom null: Hs == H and Ws == W. `vec`: the caller has checked the
+// 8-byte load conditions on the base pointer and strides (bindings.cpp im2col_u8).
+hipError_t pvr_im2col_u8(const uint8_t* img, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float* mean, const float* stdv,
+                         const float* geom, uint16_t* out, int B, int C, int Hs, int Ws, int H, int W, int P, int Kp, int vec,
+                         hipStream_t s);
+hipError_t pvr_cls_rows(const float* cls, const float* pos, uint16_t* out, int B, int D, int64_t row_stride, pvr::DropSite drop,
+                        hipStream_t s);
+hipError_t pvr_patch_bwd(const uint16_t* dE, int B, int ntok, int D, float* ws, float* dpos, float* dcls, uint16_t* dconv,
+                         float* dbias, pvr::DropSite drop, hipStream_t s);
+int pvr_patch_bwd_groups(int B);
+// floats of the scratch pvr_patch_bwd needs: the group sums and the conv-bias partials
+int64_t pvr_patch_bwd_ws_floats(int B, int ntok, int D);
+
+// ---- head.hip, xent.hip
+hipError_t pvr_head_fwd(const uint16_t* tok, int64_t ld_tok, int B, int D, const float* gamma, const float* beta, float eps,
+                        const float* W, const float* bias, int C, float* xhat, float* rstd, float* logits, hipStream_t s);
+hipError_t pvr_head_bwd(const float* dl, const float* xhat, const float* rstd, const float* gamma, const float* beta, const float* W,
+                        int B, int C, int D, int ntok, float* dW, float* db, float* dgamma, float* dbeta, float* dy, uint16_t* dtok,
+                        float* part, hipStream_t s);
+hipError_t pvr_scale_by(const float* x, const float* sc, float* y, int64_t n, hipStream_t s);
+hipError_t pvr_mean(const float* x, int n, float* out, hipStream_t s);
+hipError_t pvr_metrics_accum(float* sums, const float* loss, const int* correct, int B, hipStream_t s);
+hipError_t pvr_rng_next(int64_t* rng, int64_t* seed, hipStream_t s);
+hipError_t pvr_zero_f32(float* x, int64_t n, hipStream_t s);
+hipError_t pvr_xent(const float* logits, int64_t ld, const int64_t* labels, int B, int C, float* loss_rows, float* dlogits,
+                    int* correct, float grad_scale, hipStream_t s);
+
+// ---- optim.hip
+int pvr_norm_partial_blocks();
+// workspace: NORM_BLOCKS floats. out: 3 floats.
+hipError_t pvr_grad_norm(const float* g, int64_t n, float max_norm, float* workspace, float* out, hipStream_t s);
+// groups: device table, or null with host_groups [ngroups <= 8] copied into the kernel arguments
+hipError_t pvr_adam(float* p, const float* g, float* m, float* v, uint16_t* shadow, int64_t n, const int64_t* seg_start,
+                    const int* seg_group, int nseg, const pvr::AdamGroup* groups, const pvr::AdamGroup* host_groups, int ngroups,
+                    const float* clip, int skip_nonfinite, hipStream_t s);
+hipError_t pvr_scale_by_clip(float* g, int64_t n, const float* clip, hipStream_t s);
+// Adam with the transposed bf16 shadow (adam_t_kernel): tmeta int64 [nmat][6], fmeta int64 [nflat][4]
+// (see the kernel), flat4 = float4s covered by fmeta.
+hipError_t pvr_adam_t(float* p, const float* g, float* m, float* v, uint16_t* shadow, uint16_t* shadow_t, const int64_t* tmeta,
+                      int nmat, int ntiles, const int64_t* fmeta, int nflat, int64_t flat4, const pvr::AdamGroup* groups,
+                      const pvr::AdamGroup* host_groups, int ngroups, const float* clip, int skip_nonfinite, hipStream_t s);
+
+// ---- fp8.hip
+hipError_t pvr_fp8_quant(const uint16_t* x, int64_t ldx, uint8_t* y, int64_t ldy, int64_t rows, int cols, const float* qscale,
+                         unsigned* amax, int fmt, hipStream_t s);
+hipError_t pvr_fp8_quant_multi(const int64_t* segs, int nseg, int64_t nchunks, const float* qscale, unsigned* amax, int fmt,
+                               int amax_only, hipStream_t s);
+hipError_t pvr_fp8_quant_t(const uint16_t* x, int64_t ldx, uint8_t* y, int64_t ldy, int T, int C, const float* qscale, int fmt,
+                           hipStream_t s);
+hipError_t pvr_fp8_transpose(const uint8_t* x, int64_t ldx, uint8_t* y, int64_t ldy, int T, int C, hipStream_t s);
+hipError_t pvr_fp8_dequant(const uint8_t* x, float* y, int64_t n, const float* dscale, int fmt, hipStream_t s);
+hipError_t pvr_fp8_scale_update(float* hist, int H, unsigned* amax, float* qscale, float* dscale, const float* fmax, int s0, int s1,
+                                float margin_mul, hipStream_t s);
+
+// ---- attention.hip
+void pvr_set_attn_fwd_qg(int qg);
+void pvr_set_attn_fwd_head_qf(int qf);
+void pvr_set_attn_prep_xcd(int on);
+// diagnostic builds (-DPVR_ATTN_STAMPS): where the backward writes its phase stamps (null: nowhere)
+void pvr_set_attn_dbg(void* p);
+int pvr_attn_head_dim_supported(int dh);
+// drop: attention-probability dropout (see AttnDrop); the backward must get the same site.
+// q8: e4m3 copy of the output (row stride and base % 4); q8_only (inference): the bf16 out is unwritten
+hipError_t pvr_attn_fwd(const uint16_t* qkv, int64_t ld, uint16_t* out, int64_t ld_o, float* lse, int B, int N, int H, int D,
+                        float scale, pvr::DropSite drop, pvr::Fp8Copy q8, int q8_only, hipStream_t s);
+// ws: f32 [S][H][2 * DH] scratch, S = pvr_attn_dbias_splits(B, NQ); part f32 [B*H][NQ][3 * DH]
+int pvr_attn_dbias_splits(int B, int NQ);
+hipError_t pvr_attn_dbias_reduce(const float* part, float* ws, float* dbias, int B, int H, int NQ, int D, hipStream_t s);
+int pvr_attn_bwd_waves(int N);
+int pvr_attn_bwd_key_blocks(int N);
+// 1 if pvr_attn_bwd needs the zero-initialised f32 dQ workspace for this shape (det: deterministic
+// mode, where such shapes sum per-key-block dQ slabs in a fixed order instead: no workspace)
+int pvr_attn_bwd_needs_dq_acc(int N, int dh, int dbias, int drop, int det);
+// floats of the f32 scratch pvr_attn_bwd needs (per-query delta and, on the lastkey path, ds_last;
+// dQ slabs on the tail-split path, and in deterministic mode (det) on multi-key-block shapes without it)
+int64_t pvr_attn_bwd_ws_floats(int B, int N, int H, int D, int dbias, int drop, int det);
+// 1 if pvr_attn_bwd can write dQKV's e5m2 copy (q8.out) for this shape: the generic kernels must
+// write every final dQ value
+int pvr_attn_bwd_q8_ok(int N, int drop);
+// 1 if pvr_attn_bwd takes the pipelined whole-head backward for this shape and these layouts; its
+// dbias is then f32 [B*H][ceil(N/32)][192] partials instead: per (batch, head, 32-query block) the
+// column sums of dQ over its two 16-query halves (2 x 64, the head's q-bias slice; summed) and of dO
+// (64: the v-bias slice, sum_k dV = sum_q dO since softmax rows sum to 1); the k-bias gradient is
+// exactly 0 (sum_k dS = 0 per query)
+int pvr_attn_bwd_uses_pipe(int B, int N, int H, int D, int64_t ld, int64_t ld_do, int64_t ld_o, int64_t ld_dq, int drop);
+// Rows R of the f32 [B*H][R][3*dh] bias-gradient partials (q half 0 | q half 1 | v) that pvr_attn_bwd
+// writes for this shape: pipelined kernel (into `dbias`): R = 32-query blocks; generic kernel (into
+// `bpart`): R = 1 where attn_bwd_bpart_ok; 0: none (`dbias` then means the generic kernel's
+// [B * key blocks][3D] layout).
+int pvr_attn_bwd_part_rows(int B, int N, int H, int D, int64_t ld, int64_t ld_do, int64_t ld_o, int64_t ld_dq, int drop);
+hipError_t pvr_attn_bwd(const pvr::AttnBwdParams* p, hipStream_t s);
+
+}  // extern "C"

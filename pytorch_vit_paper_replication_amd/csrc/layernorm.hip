@@ -6,6 +6,7 @@
 // previous encoder block's fc2 dropout, mask recomputed from the same counter hash) together with
 // that layer's bias gradient (column sums of dz), so no separate pass re-reads dx for them.
 #include "common.h"
+#include "kernels.h"
 
 namespace pvr {
 namespace {
@@ -424,30 +425,25 @@ extern "C" hipError_t pvr_layernorm_fwd(const uint16_t* x, int64_t x_stride, con
 static int g_ln_q8_blocks_per_cu = 4;
 extern "C" void pvr_set_ln_fwd_q8_grid(int per_cu) { g_ln_q8_blocks_per_cu = per_cu < 1 ? 1 : per_cu > 64 ? 64 : per_cu; }
 
-// pvr_layernorm_fwd plus the e4m3 copy yq (row stride q_stride bytes) with scale *qscale and the
-// amax record (see ln_fwd_q8_kernel)
 extern "C" hipError_t pvr_layernorm_fwd_q8(const uint16_t* x, int64_t x_stride, const float* w, const float* b, uint16_t* y,
-                                           int64_t y_stride, uint8_t* yq, int64_t q_stride, const float* qscale, unsigned* amax,
-                                           float* mean, float* rstd, int rows, int D, float eps, hipStream_t s) {
+                                           int64_t y_stride, pvr::Fp8Copy q, float* mean, float* rstd, int rows, int D, float eps,
+                                           hipStream_t s) {
   using namespace pvr;
   if (rows <= 0) return hipSuccess;
-  if (D % 8 != 0 || D > 2048 || q_stride % 8 != 0) return hipErrorInvalidValue;
+  if (D % 8 != 0 || D > 2048 || q.ld % 8 != 0) return hipErrorInvalidValue;
   int nblk = (rows + 3) / 4;
   const int cap = g_ln_q8_blocks_per_cu * device_cus();
   if (nblk > cap) nblk = cap;
   const dim3 grid(nblk), block(256);
   switch ((D / 8 + 63) / 64) {
-    case 1: hipLaunchKernelGGL(ln_fwd_q8_kernel<1>, grid, block, 0, s, x, x_stride, w, b, y, y_stride, yq, q_stride, qscale, amax, mean, rstd, rows, D, eps); break;
-    case 2: hipLaunchKernelGGL(ln_fwd_q8_kernel<2>, grid, block, 0, s, x, x_stride, w, b, y, y_stride, yq, q_stride, qscale, amax, mean, rstd, rows, D, eps); break;
-    case 3: hipLaunchKernelGGL(ln_fwd_q8_kernel<3>, grid, block, 0, s, x, x_stride, w, b, y, y_stride, yq, q_stride, qscale, amax, mean, rstd, rows, D, eps); break;
-    default: hipLaunchKernelGGL(ln_fwd_q8_kernel<4>, grid, block, 0, s, x, x_stride, w, b, y, y_stride, yq, q_stride, qscale, amax, mean, rstd, rows, D, eps); break;
+    case 1: hipLaunchKernelGGL(ln_fwd_q8_kernel<1>, grid, block, 0, s, x, x_stride, w, b, y, y_stride, q.out, q.ld, q.scale, q.amax, mean, rstd, rows, D, eps); break;
+    case 2: hipLaunchKernelGGL(ln_fwd_q8_kernel<2>, grid, block, 0, s, x, x_stride, w, b, y, y_stride, q.out, q.ld, q.scale, q.amax, mean, rstd, rows, D, eps); break;
+    case 3: hipLaunchKernelGGL(ln_fwd_q8_kernel<3>, grid, block, 0, s, x, x_stride, w, b, y, y_stride, q.out, q.ld, q.scale, q.amax, mean, rstd, rows, D, eps); break;
+    default: hipLaunchKernelGGL(ln_fwd_q8_kernel<4>, grid, block, 0, s, x, x_stride, w, b, y, y_stride, q.out, q.ld, q.scale, q.amax, mean, rstd, rows, D, eps); break;
   }
   return hipGetLastError();
 }
 
-extern "C" hipError_t pvr_rows_reduce(const float* part, int R, int C, int seg, float* d0, float* d1, float* d2, hipStream_t s);
-
-// grid of the LayerNorm backward (= the partial rows [blocks][3][D] of its deterministic mode)
 extern "C" int pvr_layernorm_bwd_blocks(int rows, int D) {
   const bool use_w4 = (D / 4) % 64 == 0 && (D / 8) % 64 != 0 && D / 4 <= 64 * 5;
   // D = 768 on 4-column chunks (146 VGPRs, 3 blocks per CU): one grid of exactly the resident blocks,
@@ -457,19 +453,17 @@ extern "C" int pvr_layernorm_bwd_blocks(int rows, int D) {
   return nblk > cap ? cap : nblk;
 }
 
-extern "C" hipError_t pvr_layernorm_bwd(const uint16_t* dy, int64_t dy_stride, const uint16_t* x, int64_t x_stride,
-                                        const float* mean, const float* rstd, const float* w, const uint16_t* dres,
-                                        int64_t dres_stride, uint16_t* dx, int64_t dx_stride, float* dw, float* db,
-                                        float* dsum, uint16_t* dz, int64_t dz_stride, const uint64_t* seed_ptr,
-                                        uint64_t seed_off, uint32_t thr, float dscale, int dz_nostore, uint8_t* q, int64_t q_stride,
-                                        const float* qscale, unsigned* amax, int qfmt, int rows, int D, float* part,
-                                        hipStream_t s) {
+extern "C" hipError_t pvr_layernorm_bwd(const pvr::LnBwdParams* pp, hipStream_t s) {
   using namespace pvr;
+  const LnBwdParams& p = *pp;
+  const DropSite& d = p.drop;
+  const Fp8Copy& q = p.q;
+  const int rows = p.rows, D = p.D;
   if (rows <= 0) return hipSuccess;
-  if (qfmt != 0 && qfmt != 1) return hipErrorInvalidValue;
-  if (D % 8 != 0 || D > 1280 || (dz && (!seed_ptr || !thr))) return hipErrorInvalidValue;
-  if (q && (!qscale || !amax || q_stride % 8 != 0 || reinterpret_cast<uintptr_t>(q) % 8 != 0)) return hipErrorInvalidValue;
-  if (dz_nostore && (!dz || !q)) return hipErrorInvalidValue;  // skipping dz needs dz's fp8 copy
+  if (q.fmt != 0 && q.fmt != 1) return hipErrorInvalidValue;
+  if (D % 8 != 0 || D > 1280 || (p.dz && (!d.seed || !d.thr))) return hipErrorInvalidValue;
+  if (q.out && (!q.scale || !q.amax || q.ld % 8 != 0 || reinterpret_cast<uintptr_t>(q.out) % 8 != 0)) return hipErrorInvalidValue;
+  if (p.dz_nostore && (!p.dz || !q.out)) return hipErrorInvalidValue;  // skipping dz needs dz's fp8 copy
   // 4-column chunks (D = 768, profiles/r2s/ln_bwd_w4_ab.log): 79 -> 64 us per call (91 -> 79 with the
   // linked dropout backward); forcing 4 waves/SIMD (<= 128 VGPRs) spilled 18 VGPRs and took 114 us.
   // 4-column chunks when they tile the row over the 64 lanes exactly and 8-column ones do not
@@ -478,12 +472,12 @@ extern "C" hipError_t pvr_layernorm_bwd(const uint16_t* dy, int64_t dy_stride, c
   // (profiles/ln_bwd_grid_step_ab_r2.log); 2048 was 22 % slower in isolation, its 2048 x 3 x D column
   // atomics contending on the same addresses (profiles/kbench_ln_grid.log)
   const int nblk = pvr_layernorm_bwd_blocks(rows, D);
-  if (!dw && !db && !dsum) part = nullptr;
+  float* part = p.dw || p.db || p.dsum ? p.part : nullptr;
   const dim3 grid(nblk), block(256);
 #define PVR_LN_BWD(MC, W)                                                                                                   \
-  hipLaunchKernelGGL(q ? (ln_bwd_kernel<MC, W, true>) : (ln_bwd_kernel<MC, W, false>), grid, block, 0, s, dy, dy_stride, x, x_stride, mean, rstd, w, dres, dres_stride, dx, \
-                     dx_stride, dw, db, dsum, part, dz, dz_stride, seed_ptr, seed_off, thr, dscale, dz_nostore, q, q_stride, qscale, amax, \
-                     qfmt, rows, D)
+  hipLaunchKernelGGL(q.out ? (ln_bwd_kernel<MC, W, true>) : (ln_bwd_kernel<MC, W, false>), grid, block, 0, s, p.dy, p.dy_stride, p.x, p.x_stride, p.mean, p.rstd, p.w, p.dres, p.dres_stride, p.dx, \
+                     p.dx_stride, p.dw, p.db, p.dsum, part, p.dz, p.dz_stride, d.seed, d.offset, d.thr, d.scale, p.dz_nostore, q.out, q.ld, q.scale, q.amax, \
+                     q.fmt, rows, D)
   if (use_w4) {
     switch (D / 256) {
       case 3: PVR_LN_BWD(3, 4); break;  // D = 768
@@ -501,5 +495,5 @@ extern "C" hipError_t pvr_layernorm_bwd(const uint16_t* dy, int64_t dy_stride, c
 #undef PVR_LN_BWD
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess || !part) return e;
-  return pvr_rows_reduce(part, nblk, 3 * D, D, dw, db, dsum, s);
+  return pvr_rows_reduce(part, nblk, 3 * D, D, p.dw, p.db, p.dsum, s);
 }

@@ -7,16 +7,11 @@
 // Replaces clip_grad_norm_'s foreach kernels and torch.optim.Adam's ~7 ops per tensor
 // (reference GM/engine.py:63-66; MAIN.ipynb:2818-2824).
 #include "common.h"
+#include "kernels.h"
 
 namespace pvr {
 
-struct AdamGroup {
-  float lr, beta1, beta2, eps, weight_decay;
-  float bc1, bc2_sqrt;  // 1 - beta1^t, sqrt(1 - beta2^t)
-  int decoupled;
-};
-
-// Group table passed by value in the kernel arguments (eager stepping: no per-step host-to-device
+// Group table (AdamGroup rows: kernels.h) passed by value in the kernel arguments (eager stepping: no per-step host-to-device
 // copy); graph-captured steps pass a device table instead (kernel arguments are frozen at capture).
 constexpr int MAX_ARG_GROUPS = 8;
 struct AdamGroupArgs {
@@ -239,7 +234,6 @@ bool adam_group_args(const AdamGroup* host, int ngroups, AdamGroupArgs& out) {
 
 extern "C" int pvr_norm_partial_blocks() { return pvr::NORM_BLOCKS; }
 
-// workspace: NORM_BLOCKS floats. out: 3 floats.
 extern "C" hipError_t pvr_grad_norm(const float* g, int64_t n, float max_norm, float* workspace, float* out, hipStream_t s) {
   using namespace pvr;
   hipLaunchKernelGGL(sumsq_partial_kernel, dim3(NORM_BLOCKS), dim3(256), 0, s, g, n, workspace);
@@ -272,8 +266,6 @@ extern "C" hipError_t pvr_scale_by_clip(float* g, int64_t n, const float* clip, 
   return hipGetLastError();
 }
 
-// Adam with the transposed bf16 shadow (adam_t_kernel): tmeta int64 [nmat][6], fmeta int64 [nflat][4]
-// (see the kernel), flat4 = float4s covered by fmeta.
 extern "C" hipError_t pvr_adam_t(float* p, const float* g, float* m, float* v, uint16_t* shadow, uint16_t* shadow_t,
                                  const int64_t* tmeta, int nmat, int ntiles, const int64_t* fmeta, int nflat, int64_t flat4,
                                  const pvr::AdamGroup* groups, const pvr::AdamGroup* host_groups, int ngroups,

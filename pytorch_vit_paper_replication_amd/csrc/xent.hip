@@ -3,6 +3,7 @@
 // reduction, and the argmax==label flag per row for the accuracy metric, so the engine does not
 // need a separate softmax/argmax/eq/sum chain or a host sync per batch.
 #include "common.h"
+#include "kernels.h"
 
 namespace pvr {
 namespace {
