@@ -2055,3 +2055,260 @@ extern "C" hipError_t pvr_attn_bwd(const pvr::AttnBwdParams* pp, hipStream_t s) 
     default: return hipErrorInvalidValue;
   }
 }
+
+// ============================================================================ class-token attention
+// The last encoder block of a classifier reads only token 0 of each image: one query row per
+// (image, head). Memory-bound VALU kernels, one workgroup per (image, head): a group of DH / 8
+// neighbouring lanes owns one key row (16 B of it per lane, so a wave-instruction reads whole 2*DH-byte
+// head rows), 64 / (DH / 8) keys per wave-instruction. Q, K and V are read in place from qkv [B*N][3D].
+// No atomics: every sum has a fixed order.
+namespace pvr {
+namespace {
+
+PVR_DEV void cls_unpack8(const uint4& q, float (&f)[8]) {
+  f[0] = bf2f(q.x & 0xFFFF); f[1] = bf2f(q.x >> 16);
+  f[2] = bf2f(q.y & 0xFFFF); f[3] = bf2f(q.y >> 16);
+  f[4] = bf2f(q.z & 0xFFFF); f[5] = bf2f(q.z >> 16);
+  f[6] = bf2f(q.w & 0xFFFF); f[7] = bf2f(q.w >> 16);
+}
+PVR_DEV uint4 cls_pack8(const float (&f)[8]) {
+  return make_uint4(pack2bf(f[0], f[1]), pack2bf(f[2], f[3]), pack2bf(f[4], f[5]), pack2bf(f[6], f[7]));
+}
+PVR_DEV float cls_dot8(const float (&a)[8], const float (&b)[8]) {
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) s = fmaf(a[j], b[j], s);
+  return s;
+}
+// sum over the CH lanes gbase .. gbase + CH - 1 of a key group (every lane of the group receives it,
+// added in the same order); executed by the whole wave
+template <int CH>
+PVR_DEV float cls_group_sum(float v, int gbase) {
+  if constexpr (CH == 8) {
+    return oct_sum(v);
+  } else if constexpr (CH == 16) {
+    return row16_sum(v);
+  } else {
+    float t = 0.f;
+#pragma unroll
+    for (int j = 0; j < CH; ++j) t += __shfl(v, min(gbase + j, 63), 64);
+    return t;
+  }
+}
+template <bool MAX>
+PVR_DEV float cls_block_reduce(float v, float* r4) {
+  v = MAX ? wave_max(v) : wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) r4[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return MAX ? fmaxf(fmaxf(r4[0], r4[1]), fmaxf(r4[2], r4[3])) : (r4[0] + r4[1]) + (r4[2] + r4[3]);
+}
+
+// out[b][h*DH ..] = softmax(q_0 K^T * scale) V of pair (b, h), lse[b*H + h] = its log-sum-exp (natural).
+// Dynamic LDS: N floats (the scores, then the unnormalised probabilities).
+template <int DH>
+__global__ void __launch_bounds__(256) attn_cls_fwd_kernel(const uint16_t* __restrict__ qkv, int64_t ld, uint16_t* __restrict__ out,
+                                                            int64_t ld_o, float* __restrict__ lse, int N, int H, int D, float scale) {
+  constexpr int CH = DH / 8, GPW = 64 / CH, NG = 4 * GPW;
+  extern __shared__ float cls_sc[];
+  __shared__ float gred[NG * DH];
+  __shared__ float r4[4];
+  const int bh = blockIdx.x, b = bh / H, h = bh % H;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = lane / CH, c = lane % CH;
+  const bool act = g < GPW;
+  const uint16_t* base = qkv + (int64_t)b * N * ld + h * DH + c * 8;
+  float qf[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) qf[j] = 0.f;
+  if (act) cls_unpack8(*(const uint4*)base, qf);
+  for (int k0 = wave * GPW; k0 < N; k0 += NG) {  // wave-uniform trip count
+    const int k = k0 + g;
+    const bool live = act && k < N;
+    float sv = 0.f;
+    if (live) {
+      float kf[8];
+      cls_unpack8(*(const uint4*)(base + (int64_t)k * ld + D), kf);
+      sv = cls_dot8(qf, kf);
+    }
+    sv = cls_group_sum<CH>(sv, g * CH);
+    if (live && c == 0) cls_sc[k] = sv * scale;
+  }
+  __syncthreads();
+  float m = -INFINITY;
+  for (int k = tid; k < N; k += 256) m = fmaxf(m, cls_sc[k]);
+  m = cls_block_reduce<true>(m, r4);
+  float l = 0.f;
+  for (int k = tid; k < N; k += 256) {
+    const float pk = __builtin_amdgcn_exp2f((cls_sc[k] - m) * LOG2E);
+    cls_sc[k] = pk;
+    l += pk;
+  }
+  l = cls_block_reduce<false>(l, r4);  // (its barriers also publish the probabilities)
+  if (tid == 0) lse[bh] = m + logf(l);
+  float acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+  if (act) {
+    for (int k = wave * GPW + g; k < N; k += NG) {
+      float vf[8];
+      cls_unpack8(*(const uint4*)(base + (int64_t)k * ld + 2 * D), vf);
+      const float pk = cls_sc[k];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] = fmaf(pk, vf[j], acc[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) gred[(wave * GPW + g) * DH + c * 8 + j] = acc[j];
+  }
+  __syncthreads();
+  if (tid < DH) {
+    float o = 0.f;
+#pragma unroll 4
+    for (int gg = 0; gg < NG; ++gg) o += gred[gg * DH + tid];
+    out[(int64_t)b * ld_o + h * DH + tid] = f2bf(o / l);
+  }
+}
+
+// Backward of attn_cls_fwd_kernel from dO_0 (dout [B][D]), o_0 (o [B][D]) and lse [B*H]: one pass over K
+// and V. P_0k = exp(q_0.K_k * scale - lse), dS_0k = P_0k (dO_0.V_k - delta_0), delta_0 = dO_0.o_0;
+// writes dV_k = P_0k dO_0 and dK_k = dS_0k q_0 * scale for every key row, dQ_0 = sum_k dS_0k K_k * scale
+// into the token-0 row and zeros into the other dQ rows of dqkv [B*N][3D]; dq0 [B][D] f32 receives dQ_0
+// unrounded (the q slice of the in_proj bias gradient sums it).
+template <int DH>
+__global__ void __launch_bounds__(256) attn_cls_bwd_kernel(const uint16_t* __restrict__ qkv, int64_t ld, const uint16_t* __restrict__ o,
+                                                            int64_t ld_o, const uint16_t* __restrict__ dout, int64_t ld_do,
+                                                            const float* __restrict__ lse, uint16_t* __restrict__ dqkv, int64_t ld_dq,
+                                                            float* __restrict__ dq0, int N, int H, int D, float scale) {
+  constexpr int CH = DH / 8, GPW = 64 / CH, NG = 4 * GPW;
+  __shared__ float gred[NG * DH];
+  const int bh = blockIdx.x, b = bh / H, h = bh % H;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = lane / CH, c = lane % CH;
+  const bool act = g < GPW;
+  const int col = h * DH + c * 8;
+  const uint16_t* base = qkv + (int64_t)b * N * ld + col;
+  uint16_t* dbase = dqkv + (int64_t)b * N * ld_dq + col;
+  float qf[8], dof[8], dqa[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) qf[j] = dof[j] = dqa[j] = 0.f;
+  float dpart = 0.f;
+  if (act) {
+    float of[8];
+    cls_unpack8(*(const uint4*)base, qf);
+    cls_unpack8(*(const uint4*)(dout + (int64_t)b * ld_do + col), dof);
+    cls_unpack8(*(const uint4*)(o + (int64_t)b * ld_o + col), of);
+    dpart = cls_dot8(dof, of);
+  }
+  const float delta = cls_group_sum<CH>(dpart, g * CH);
+  const float l2 = lse[bh] * LOG2E, sl2 = scale * LOG2E;
+  for (int k0 = wave * GPW; k0 < N; k0 += NG) {  // wave-uniform trip count
+    const int k = k0 + g;
+    const bool live = act && k < N;
+    float kf[8], vf[8];
+    float sv = 0.f, tv = 0.f;
+    if (live) {
+      const uint4 kq = *(const uint4*)(base + (int64_t)k * ld + D);
+      const uint4 vq = *(const uint4*)(base + (int64_t)k * ld + 2 * D);
+      cls_unpack8(kq, kf);
+      cls_unpack8(vq, vf);
+      sv = cls_dot8(qf, kf);
+      tv = cls_dot8(dof, vf);
+    }
+    sv = cls_group_sum<CH>(sv, g * CH);
+    tv = cls_group_sum<CH>(tv, g * CH);
+    if (live) {
+      const float pk = __builtin_amdgcn_exp2f(sv * sl2 - l2);
+      const float ds = pk * (tv - delta) * scale;
+      float dk[8], dv[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        dv[j] = pk * dof[j];
+        dk[j] = ds * qf[j];
+        dqa[j] = fmaf(ds, kf[j], dqa[j]);
+      }
+      uint16_t* row = dbase + (int64_t)k * ld_dq;
+      if (k > 0) *(uint4*)row = make_uint4(0u, 0u, 0u, 0u);
+      *(uint4*)(row + D) = cls_pack8(dk);
+      *(uint4*)(row + 2 * D) = cls_pack8(dv);
+    }
+  }
+  if (act) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) gred[(wave * GPW + g) * DH + c * 8 + j] = dqa[j];
+  }
+  __syncthreads();
+  if (tid < DH) {
+    float dq = 0.f;
+#pragma unroll 4
+    for (int gg = 0; gg < NG; ++gg) dq += gred[gg * DH + tid];
+    dqkv[(int64_t)b * N * ld_dq + h * DH + tid] = f2bf(dq);
+    dq0[(int64_t)b * D + h * DH + tid] = dq;
+  }
+}
+
+// in_proj bias gradient of the class-token attention: dbias[c] += sum_b dQ_0[b][c] (q slice),
+// dbias[2D + c] += sum_b dO_0[b][c] (v slice: sum_k dV_k = dO_0, the probabilities sum to 1); the k slice
+// gets nothing (sum_k dS_0k = 0). One thread per column, images in order.
+__global__ void __launch_bounds__(256) attn_cls_dbias_kernel(const float* __restrict__ dq0, const uint16_t* __restrict__ dout,
+                                                              int64_t ld_do, float* __restrict__ dbias, int B, int D) {
+  const int col = blockIdx.x * 256 + threadIdx.x;
+  if (col >= D) return;
+  float sq = 0.f, sv = 0.f;
+#pragma unroll 8
+  for (int b = 0; b < B; ++b) {
+    sq += dq0[(int64_t)b * D + col];
+    sv += bf2f(dout[(int64_t)b * ld_do + col]);
+  }
+  dbias[col] += sq;
+  dbias[2 * D + col] += sv;
+}
+
+bool attn_cls_args_ok(int B, int N, int H, int D, int64_t ld, int64_t ld_o) {
+  return B > 0 && N > 0 && H > 0 && D % H == 0 && pvr_attn_cls_ok(N, D / H) && ld % 8 == 0 && ld_o % 8 == 0 && ld >= 3 * (int64_t)D &&
+         ld_o >= D;
+}
+
+}  // namespace
+}  // namespace pvr
+
+// 1 if the class-token attention kernels take this shape (the forward keeps N scores in LDS)
+extern "C" int pvr_attn_cls_ok(int N, int dh) { return N >= 1 && N <= 8192 && pvr_attn_head_dim_supported(dh) ? 1 : 0; }
+
+extern "C" hipError_t pvr_attn_cls_fwd(const uint16_t* qkv, int64_t ld, uint16_t* out, int64_t ld_o, float* lse, int B, int N, int H,
+                                       int D, float scale, hipStream_t s) {
+  using namespace pvr;
+  if (!attn_cls_args_ok(B, N, H, D, ld, ld_o)) return hipErrorInvalidValue;
+  const dim3 grid(B * H), block(256);
+  const size_t smem = (size_t)N * sizeof(float);
+  switch (D / H) {
+#define PVR_CLS_DH(DH) \
+  case DH: hipLaunchKernelGGL(attn_cls_fwd_kernel<DH>, grid, block, smem, s, qkv, ld, out, ld_o, lse, N, H, D, scale); break;
+    PVR_CLS_DH(64) PVR_CLS_DH(80) PVR_CLS_DH(96) PVR_CLS_DH(128)
+#undef PVR_CLS_DH
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+extern "C" hipError_t pvr_attn_cls_bwd(const uint16_t* qkv, int64_t ld, const uint16_t* o, int64_t ld_o, const uint16_t* dout,
+                                       int64_t ld_do, const float* lse, uint16_t* dqkv, int64_t ld_dq, float* dq0, int B, int N, int H,
+                                       int D, float scale, hipStream_t s) {
+  using namespace pvr;
+  if (!attn_cls_args_ok(B, N, H, D, ld, ld_o) || ld_do % 8 != 0 || ld_do < D || ld_dq % 8 != 0 || ld_dq < 3 * (int64_t)D)
+    return hipErrorInvalidValue;
+  const dim3 grid(B * H), block(256);
+  switch (D / H) {
+#define PVR_CLS_DH(DH) \
+  case DH: hipLaunchKernelGGL(attn_cls_bwd_kernel<DH>, grid, block, 0, s, qkv, ld, o, ld_o, dout, ld_do, lse, dqkv, ld_dq, dq0, N, H, D, scale); break;
+    PVR_CLS_DH(64) PVR_CLS_DH(80) PVR_CLS_DH(96) PVR_CLS_DH(128)
+#undef PVR_CLS_DH
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+extern "C" hipError_t pvr_attn_cls_dbias(const float* dq0, const uint16_t* dout, int64_t ld_do, float* dbias, int B, int D, hipStream_t s) {
+  if (B <= 0 || D <= 0 || ld_do < D) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(pvr::attn_cls_dbias_kernel, dim3((D + 255) / 256), dim3(256), 0, s, dq0, dout, ld_do, dbias, B, D);
+  return hipGetLastError();
+}

@@ -187,8 +187,12 @@ void gemm(torch::Tensor A, bool a_kcontig, torch::Tensor B, bool b_kcontig, torc
           int64_t addend_period, c10::optional<torch::Tensor> aux, int64_t row_group, int64_t row_stride_group,
           int64_t row_offset, c10::optional<torch::Tensor> seed, int64_t seed_offset, double drop_p, int64_t k_split,
           int64_t tile_cfg, c10::optional<torch::Tensor> dbg, c10::optional<torch::Tensor> colsum,
-          int64_t epi_staged, int64_t tail_limit, c10::optional<torch::Tensor> reduce_out, bool reduce_acc) {
+          int64_t epi_staged, int64_t tail_limit, c10::optional<torch::Tensor> reduce_out, bool reduce_acc,
+          int64_t drop_row_mul) {
   pvr::GemmParams p{};
+  TORCH_CHECK(drop_row_mul >= 0 && (drop_row_mul == 0 || (tile_cfg == 0 && row_group == 0)) && M * std::max<int64_t>(drop_row_mul, 1) < (int64_t(1) << 31),
+              "gemm: drop_row_mul (mask of every drop_row_mul-th row of a larger tensor) needs tile 0 and no row remap");
+  p.drop_row_mul = (int)drop_row_mul;
   p.epi_staged = (int)epi_staged;
   if (colsum.has_value() && colsum->defined()) p.colsum = f32_mut(*colsum, "colsum");
   if (dbg.has_value() && dbg->defined()) p.dbg = reinterpret_cast<uint64_t*>(dbg->data_ptr());
@@ -299,9 +303,16 @@ void layernorm_bwd(torch::Tensor dy, int64_t dy_stride, torch::Tensor x, int64_t
                    c10::optional<torch::Tensor> dsum, c10::optional<torch::Tensor> dz, c10::optional<torch::Tensor> seed,
                    int64_t seed_offset, double drop_p, c10::optional<torch::Tensor> q_out,
                    c10::optional<torch::Tensor> q_scale, c10::optional<torch::Tensor> q_amax, bool dz_nostore,
-                   int64_t q_fmt) {
+                   int64_t q_fmt, int64_t dres_every) {
   const int64_t D = w.numel();
   pvr::LnBwdParams p{};
+  TORCH_CHECK(dres_every >= 0, "layernorm_bwd: dres_every >= 0");
+  if (dres_every > 1) {
+    TORCH_CHECK(dres.has_value() && dres->defined() && dres->numel() >= ((rows + dres_every - 1) / dres_every - 1) * dres_stride + D &&
+                    !(q_out.has_value() && q_out->defined()),
+                "layernorm_bwd: dres_every needs a compact dres [ceil(rows / dres_every)][D] and no fp8 copy");
+  }
+  p.dres_every = (int)dres_every;
   p.dy = bf(dy, "dy"); p.dy_stride = dy_stride;
   p.x = bf(x, "x"); p.x_stride = x_stride;
   p.mean = f32(mean, "mean"); p.rstd = f32(rstd, "rstd"); p.w = f32(w, "w");
@@ -389,7 +400,8 @@ void transpose_batched(torch::Tensor src, torch::Tensor dst, torch::Tensor meta,
 
 void colsum(torch::Tensor dy, int64_t rows, int64_t N, c10::optional<torch::Tensor> db, c10::optional<torch::Tensor> dz,
             c10::optional<torch::Tensor> seed, int64_t seed_offset, double drop_p, c10::optional<torch::Tensor> q_out,
-            c10::optional<torch::Tensor> q_scale, c10::optional<torch::Tensor> q_amax, int64_t q_fmt) {
+            c10::optional<torch::Tensor> q_scale, c10::optional<torch::Tensor> q_amax, int64_t q_fmt, int64_t row_mul) {
+  TORCH_CHECK(row_mul >= 1 && rows * row_mul < (int64_t(1) << 31), "colsum: row_mul >= 1 and rows * row_mul < 2^31");
   const pvr::DropSite d = drop_args(seed, seed_offset, drop_p, "colsum");
   int64_t ldz = 0;
   uint16_t* dzp = nullptr;
@@ -397,7 +409,8 @@ void colsum(torch::Tensor dy, int64_t rows, int64_t N, c10::optional<torch::Tens
   // optional fp8 copy (q_fmt 1 e5m2, 0 e4m3) of the (masked) gradient + amax record (the fp8 dgrad operand)
   const pvr::Fp8Copy q = fp8_copy(q_out, q_scale, q_amax, q_fmt, rows, N, 8, "colsum");
   check(pvr_colsum(bf(dy, "dy"), ld_of(dy, "dy"), (int)rows, (int)N, opt_ptr<float>(db), dzp, ldz, d, q,
-                   g_deterministic && opt_ptr<float>(db) ? det_scratch((int64_t)pvr_colsum_part_rows((int)rows) * N, dy.options()) : nullptr, stream()),
+                   g_deterministic && opt_ptr<float>(db) ? det_scratch((int64_t)pvr_colsum_part_rows((int)rows) * N, dy.options()) : nullptr,
+                   (int)row_mul, stream()),
         "colsum");
 }
 
@@ -990,6 +1003,49 @@ torch::Tensor attn_bwd(torch::Tensor dout, torch::Tensor qkv, torch::Tensor out,
   return dqkv;
 }
 
+// Class-token attention forward (csrc/attention.hip): qkv [B*N][3D] -> {o_0 [B][D] bf16, lse_0 [B*H] f32}
+// of each image's token-0 query (no attention dropout)
+std::vector<torch::Tensor> attn_cls_fwd(torch::Tensor qkv, int64_t B, int64_t N, int64_t H, double scale) {
+  TORCH_CHECK(qkv.dim() == 2 && qkv.size(0) == B * N && qkv.size(1) % 3 == 0 && H > 0, "attn_cls_fwd: qkv [B*N][3D]");
+  const int64_t D = qkv.size(1) / 3;
+  TORCH_CHECK(D % H == 0 && pvr_attn_cls_ok((int)N, (int)(D / H)), "attn_cls_fwd: unsupported N / head dim (attn_cls_ok)");
+  auto out = torch::empty({B, D}, qkv.options());
+  auto lse = torch::empty({B * H}, qkv.options().dtype(torch::kFloat32));
+  check(pvr_attn_cls_fwd(bf(qkv, "qkv"), ld_of(qkv, "qkv"), bf_mut(out, "out"), D, f32_mut(lse, "lse"), (int)B, (int)N, (int)H, (int)D,
+                         (float)scale, stream()),
+        "attn_cls_fwd");
+  return {out, lse};
+}
+
+// Class-token attention backward: returns {dqkv [B*N][3D] bf16 (dQ rows other than token 0 zero), dq0 [B][D]
+// f32}; dbias [3D] f32 (optional) accumulates the in_proj bias gradient
+std::vector<torch::Tensor> attn_cls_bwd(torch::Tensor dout, torch::Tensor qkv, torch::Tensor out, torch::Tensor lse, int64_t B, int64_t N,
+                                        int64_t H, double scale) {
+  TORCH_CHECK(qkv.dim() == 2 && qkv.size(0) == B * N && qkv.size(1) % 3 == 0 && H > 0, "attn_cls_bwd: qkv [B*N][3D]");
+  const int64_t D = qkv.size(1) / 3;
+  TORCH_CHECK(D % H == 0 && pvr_attn_cls_ok((int)N, (int)(D / H)), "attn_cls_bwd: unsupported N / head dim (attn_cls_ok)");
+  TORCH_CHECK(dout.dim() == 2 && dout.size(0) == B && dout.size(1) == D && out.dim() == 2 && out.size(0) == B && out.size(1) == D &&
+                  lse.numel() == B * H && lse.is_contiguous(),
+              "attn_cls_bwd: dout / out [B][D], lse [B*H]");
+  auto dqkv = torch::empty({B * N, 3 * D}, qkv.options());
+  auto dq0 = torch::empty({B, D}, qkv.options().dtype(torch::kFloat32));
+  check(pvr_attn_cls_bwd(bf(qkv, "qkv"), ld_of(qkv, "qkv"), bf(out, "out"), ld_of(out, "out"), bf(dout, "dout"), ld_of(dout, "dout"),
+                         f32(lse, "lse"), bf_mut(dqkv, "dqkv"), 3 * D, f32_mut(dq0, "dq0"), (int)B, (int)N, (int)H, (int)D, (float)scale,
+                         stream()),
+        "attn_cls_bwd");
+  return {dqkv, dq0};
+}
+
+// dbias [3D] f32 += in_proj bias gradient of the class-token attention from dq0 [B][D] f32 and dout [B][D] bf16
+void attn_cls_dbias(torch::Tensor dq0, torch::Tensor dout, torch::Tensor dbias) {
+  TORCH_CHECK(dq0.dim() == 2 && dq0.is_contiguous() && dout.dim() == 2 && dout.size(0) == dq0.size(0) && dout.size(1) == dq0.size(1) &&
+                  dbias.is_contiguous() && dbias.numel() == 3 * dq0.size(1),
+              "attn_cls_dbias: dq0 f32 [B][D] contiguous, dout bf16 [B][D], dbias f32 [3D]");
+  check(pvr_attn_cls_dbias(f32(dq0, "dq0"), bf(dout, "dout"), ld_of(dout, "dout"), f32_mut(dbias, "dbias"), (int)dq0.size(0),
+                           (int)dq0.size(1), stream()),
+        "attn_cls_dbias");
+}
+
 }  // namespace
 
 extern "C" const char* pvr_src_hash(void);  // _build/src_hash.c (build.py): hash of csrc/*
@@ -1018,7 +1074,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("addend_period"), py::arg("aux"), py::arg("row_group"), py::arg("row_stride_group"),
         py::arg("row_offset"), py::arg("seed"), py::arg("seed_offset"), py::arg("drop_p"), py::arg("k_split"),
         py::arg("tile_cfg"), py::arg("dbg") = py::none(), py::arg("colsum") = py::none(),
-        py::arg("epi_staged") = 0, py::arg("tail_limit") = 0, py::arg("reduce_out") = py::none(), py::arg("reduce_acc") = true);
+        py::arg("epi_staged") = 0, py::arg("tail_limit") = 0, py::arg("reduce_out") = py::none(), py::arg("reduce_acc") = true,
+        py::arg("drop_row_mul") = 0);
   m.def("splitk_timeouts", &splitk_timeouts, py::arg("like"), py::arg("reset") = false);
   m.def("num_cus", &num_cus);
   m.def("layernorm_fwd", &layernorm_fwd);
@@ -1029,7 +1086,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dx_stride"), py::arg("dw"), py::arg("db"), py::arg("rows"), py::arg("dsum") = py::none(),
         py::arg("dz") = py::none(), py::arg("seed") = py::none(), py::arg("seed_offset") = 0, py::arg("drop_p") = 0.0,
         py::arg("q_out") = py::none(), py::arg("q_scale") = py::none(), py::arg("q_amax") = py::none(),
-        py::arg("dz_nostore") = false, py::arg("q_fmt") = 1);
+        py::arg("dz_nostore") = false, py::arg("q_fmt") = 1, py::arg("dres_every") = 0);
   m.def("cast_f32_bf16", &cast_f32_bf16);
   m.def("splitk_epilogue", &splitk_epilogue);
   m.def("attn_bwd_bias_rows", &attn_bwd_bias_rows, py::arg("B"), py::arg("N"), py::arg("H"), py::arg("D"), py::arg("drop") = false);
@@ -1039,7 +1096,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("transpose_batched", &transpose_batched);
   m.def("colsum", &colsum, py::arg("dy"), py::arg("rows"), py::arg("N"), py::arg("db"), py::arg("dz"), py::arg("seed"),
         py::arg("seed_offset"), py::arg("drop_p"), py::arg("q_out") = py::none(), py::arg("q_scale") = py::none(),
-        py::arg("q_amax") = py::none(), py::arg("q_fmt") = 1);
+        py::arg("q_amax") = py::none(), py::arg("q_fmt") = 1, py::arg("row_mul") = 1);
   m.def("im2col", &im2col);
   m.def("im2col_u8", &im2col_u8, py::arg("img"), py::arg("out"), py::arg("mean"), py::arg("std"), py::arg("geom"), py::arg("H"),
         py::arg("W"), py::arg("P"), py::arg("Kp"));
@@ -1084,6 +1141,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("seed") = py::none(), py::arg("seed_offset") = 0, py::arg("drop_p") = 0.0, py::arg("q_out") = py::none(),
         py::arg("q_scale") = py::none(), py::arg("q_amax") = py::none(), py::arg("q_only") = false,
         py::arg("q_fmt") = 1);
+  m.def("attn_cls_ok", [](int64_t N, int64_t dh) { return pvr_attn_cls_ok((int)N, (int)dh) != 0; },
+        "the class-token attention kernels take this token count and head dim");
+  m.def("attn_cls_fwd", &attn_cls_fwd, py::arg("qkv"), py::arg("B"), py::arg("N"), py::arg("H"), py::arg("scale"));
+  m.def("attn_cls_bwd", &attn_cls_bwd, py::arg("dout"), py::arg("qkv"), py::arg("out"), py::arg("lse"), py::arg("B"), py::arg("N"),
+        py::arg("H"), py::arg("scale"));
+  m.def("attn_cls_dbias", &attn_cls_dbias);
   m.def("attn_bwd_q8_ok", &attn_bwd_q8_ok, "attn_bwd can write dQKV's e5m2 copy for this shape");
   m.def("arch", []() { return std::string("gfx950"); });
 }

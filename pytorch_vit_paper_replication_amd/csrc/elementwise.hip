@@ -25,7 +25,8 @@ __global__ void __launch_bounds__(256) cast_f32_bf16_kernel(const float* __restr
 }
 
 // dY [rows][N] (row stride ld) -> db[N] += column sums of (mask * dY); if dz != null also writes
-// the masked gradient dz (= dropout backward) with row stride ld_dz.
+// the masked gradient dz (= dropout backward) with row stride ld_dz. row_mul: the mask of row r is that of row
+// r * row_mul of a larger [rows * row_mul][N] tensor (1: this one; > 1: its class-token rows, compact).
 // Q8: also the fp8 copy (qfmt 1 e5m2, 0 e4m3) of the (masked) gradient, q[r][n] = fp8(v * *qscale), and its amax record
 // (the fp8 dgrad operand of the same tensor whose column sums are the bias gradient: one read, two uses)
 template <bool Q8>
@@ -33,7 +34,7 @@ __global__ void __launch_bounds__(256) colsum_kernel(const uint16_t* __restrict_
                                                       float* __restrict__ db, uint16_t* __restrict__ dz, int64_t ld_dz,
                                                       const uint64_t* seed_ptr, uint64_t seed_off, uint32_t thr, float scale,
                                                       uint8_t* __restrict__ qout, int64_t ld_q, const float* __restrict__ qscale,
-                                                      unsigned* __restrict__ amax, int qfmt, float* __restrict__ part) {
+                                                      unsigned* __restrict__ amax, int qfmt, float* __restrict__ part, int row_mul) {
   __shared__ float red[4][64 * 8];
   const float qs = Q8 ? *qscale : 1.f;
   float qam = 0.f;
@@ -66,7 +67,7 @@ __global__ void __launch_bounds__(256) colsum_kernel(const uint16_t* __restrict_
 #pragma unroll
           for (int j = 0; j < 8; j += 2) {
             bool k0, k1;
-            rng_keep2(seed, (uint64_t)r * N + c * 8 + j, thr, k0, k1);
+            rng_keep2(seed, (uint64_t)r * row_mul * N + c * 8 + j, thr, k0, k1);
             v[j] = k0 ? v[j] * scale : 0.f;
             v[j + 1] = k1 ? v[j + 1] * scale : 0.f;
           }
@@ -576,16 +577,17 @@ extern "C" int pvr_colsum_part_rows(int rows) {
 }
 
 extern "C" hipError_t pvr_colsum(const uint16_t* dy, int64_t ld, int rows, int N, float* db, uint16_t* dz, int64_t ld_dz,
-                                 pvr::DropSite drop, pvr::Fp8Copy q, float* part, hipStream_t s) {
+                                 pvr::DropSite drop, pvr::Fp8Copy q, float* part, int row_mul, hipStream_t s) {
   using namespace pvr;
   if (rows <= 0) return hipSuccess;
+  if (row_mul < 1 || (int64_t)rows * row_mul >= (1ll << 31)) return hipErrorInvalidValue;
   if (N % 8 != 0 || (q.fmt != 0 && q.fmt != 1)) return hipErrorInvalidValue;
   if (q.out && (!q.scale || !q.amax || q.ld % 8 != 0 || reinterpret_cast<uintptr_t>(q.out) % 8 != 0)) return hipErrorInvalidValue;
   const int gx = (N / 8 + 63) / 64;
   const int gy = pvr_colsum_part_rows(rows);
   if (!db) part = nullptr;
   hipLaunchKernelGGL(q.out ? colsum_kernel<true> : colsum_kernel<false>, dim3(gx, gy), dim3(256), 0, s, dy, ld, rows, N, db, dz, ld_dz,
-                     drop.seed, drop.offset, drop.thr, drop.scale, q.out, q.ld, q.scale, q.amax, q.fmt, part);
+                     drop.seed, drop.offset, drop.thr, drop.scale, q.out, q.ld, q.scale, q.amax, q.fmt, part, row_mul);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || !part) return e;
   return pvr_rows_reduce(part, gy, N, N, db, nullptr, nullptr, s);

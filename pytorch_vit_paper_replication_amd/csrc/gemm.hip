@@ -194,7 +194,7 @@ PVR_DEV void epilogue(const GemmParams& p, v4f (&acc)[FM][FN], int mb, int nb, i
           bool keep[4] = {true, true, true, true};
           if constexpr (EPI == EPI_BF16 || EPI == EPI_GELU) {
             if (p.drop_thr) {
-              const uint64_t idx = (uint64_t)orow * p.N + n;
+              const uint64_t idx = (uint64_t)(p.drop_row_mul ? (int64_t)m * p.drop_row_mul : orow) * p.N + n;
               rng_keep2(seed, idx, p.drop_thr, keep[0], keep[1]);
               rng_keep2(seed, idx + 2, p.drop_thr, keep[2], keep[3]);
             }
@@ -2085,6 +2085,8 @@ extern "C" hipError_t pvr_gemm(const pvr::GemmParams* pp, hipStream_t s) {
   using namespace pvr;
   const GemmParams& p = *pp;
   if (p.M <= 0 || p.N <= 0 || p.K <= 0) return hipSuccess;
+  // compact class-token rows with the full tensor's dropout mask: the shared epilogue of the 128x128 tiles
+  if (p.drop_row_mul && (p.drop_row_mul < 0 || p.tile_cfg != 0 || p.row_group || p.elem8)) return hipErrorInvalidValue;
   // tile 15: wave-specialized persistent kernel (epilogue waves beside the MFMA waves); shapes it
   // does not take fall through to the 256x256 ping-pong
   if (p.tile_cfg == 15) {

@@ -56,6 +56,11 @@ struct GemmParams {
   // overwrite). Needs every workgroup of the launch co-resident (host: tiles x splits <= CUs).
   // sk_cnt[2 * sk_cnt_tiles] counts spin timeouts (0 in a healthy run).
   float* sk_out; int64_t sk_ldo; unsigned* sk_cnt; int sk_acc; int sk_cnt_tiles;
+  // drop_row_mul > 0: the M rows are a compact copy of every drop_row_mul-th row of a larger
+  // [M * drop_row_mul][N] tensor (the class-token rows of a token matrix): the dropout mask of row m is
+  // that of row m * drop_row_mul there, while loads and stores use m. The 128x128 tiles (tile_cfg 0)
+  // only; without row_group.
+  int drop_row_mul;
 };
 
 }  // namespace pvr

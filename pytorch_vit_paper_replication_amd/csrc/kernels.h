@@ -40,6 +40,9 @@ struct LnBwdParams {
   const uint16_t* x; int64_t x_stride;
   const float* mean; const float* rstd; const float* w;
   const uint16_t* dres; int64_t dres_stride;  // optional
+  // dres_every > 1: only rows r % dres_every == 0 have a residual gradient, row r / dres_every of the
+  // compact dres [ceil(rows / dres_every)][D] (the class-token rows); not with the fp8 copy q
+  int dres_every;
   uint16_t* dx; int64_t dx_stride;
   float* dw; float* db; float* dsum;
   // dz (optional, needs drop.seed): dz = mask * scale * dx, the dropout backward of the layer that
@@ -117,9 +120,10 @@ hipError_t pvr_transpose_batched(const uint16_t* src, uint16_t* dst, const int64
 int pvr_colsum_part_rows(int rows);
 // db (optional) += column sums of dy, or of dz = mask * scale * dy when drop.seed is set; dz
 // (optional) receives that product, q its fp8 copy (row stride and base % 8); part: deterministic
-// mode scratch [pvr_colsum_part_rows][N]
+// mode scratch [pvr_colsum_part_rows][N]; row_mul >= 1: row r takes the dropout mask of row r * row_mul
+// (the compact class-token rows of a [rows * row_mul][N] tensor)
 hipError_t pvr_colsum(const uint16_t* dy, int64_t ld, int rows, int N, float* db, uint16_t* dz, int64_t ld_dz, pvr::DropSite drop,
-                      pvr::Fp8Copy q, float* part, hipStream_t s);
+                      pvr::Fp8Copy q, float* part, int row_mul, hipStream_t s);
 // d0/d1/d2[c % seg] += sum over the R rows of part[R][C] (row order: deterministic)
 hipError_t pvr_rows_reduce(const float* part, int R, int C, int seg, float* d0, float* d1, float* d2, hipStream_t s);
 hipError_t pvr_im2col(const float* img, uint16_t* out, int B, int C, int H, int W, int P, int Kp, hipStream_t s);
@@ -214,5 +218,18 @@ int pvr_attn_bwd_uses_pipe(int B, int N, int H, int D, int64_t ld, int64_t ld_do
 // [B * key blocks][3D] layout).
 int pvr_attn_bwd_part_rows(int B, int N, int H, int D, int64_t ld, int64_t ld_do, int64_t ld_o, int64_t ld_dq, int drop);
 hipError_t pvr_attn_bwd(const pvr::AttnBwdParams* p, hipStream_t s);
+// Class-token attention (the last encoder block of a classifier: one query, token 0, per image and
+// head; no attention dropout). 1 if the kernels take this shape (any N in [1, 8192], the head dims above)
+int pvr_attn_cls_ok(int N, int dh);
+// out [B][D] (row stride ld_o) = softmax(q_0 K^T * scale) V per (image, head), lse f32 [B*H]
+hipError_t pvr_attn_cls_fwd(const uint16_t* qkv, int64_t ld, uint16_t* out, int64_t ld_o, float* lse, int B, int N, int H, int D,
+                            float scale, hipStream_t s);
+// dqkv [B*N][3D] (every element written: dQ rows other than token 0 are zero) from dout / o [B][D] and
+// lse [B*H]; dq0 f32 [B][D] receives dQ_0 unrounded
+hipError_t pvr_attn_cls_bwd(const uint16_t* qkv, int64_t ld, const uint16_t* o, int64_t ld_o, const uint16_t* dout, int64_t ld_do,
+                            const float* lse, uint16_t* dqkv, int64_t ld_dq, float* dq0, int B, int N, int H, int D, float scale,
+                            hipStream_t s);
+// dbias [3D] += the in_proj bias gradient: column sums of dq0 (q slice) and of dout (v slice), images in order
+hipError_t pvr_attn_cls_dbias(const float* dq0, const uint16_t* dout, int64_t ld_do, float* dbias, int B, int D, hipStream_t s);
 
 }  // extern "C"

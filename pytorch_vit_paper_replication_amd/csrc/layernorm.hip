@@ -204,7 +204,9 @@ struct RowVec<4> {
 // D / 4 is (D = 768: 3 chunks of 4 per lane instead of 1.5 of 8, so no lane idles on the last chunk
 // and the smaller register footprint doubles the waves in flight: 4 per SIMD instead of 2).
 // Q8: the fp8-copy variant (qout / dz_nostore used); the bf16 instantiation carries none of it.
-template <int MAXCH, int W, bool Q8>
+// SP: the residual gradient exists on every dres_every-th row only (the class-token rows), read from
+// the compact dres [rows / dres_every][D]; the other rows get LN'(dy) alone.
+template <int MAXCH, int W, bool Q8, bool SP>
 __global__ void __launch_bounds__(256) ln_bwd_kernel(const uint16_t* __restrict__ dy, int64_t dy_stride,
                                                       const uint16_t* __restrict__ x, int64_t x_stride,
                                                       const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -217,7 +219,7 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const uint16_t* __restrict_
                                                       const uint64_t* __restrict__ seed_ptr, uint64_t seed_off, uint32_t thr,
                                                       float dscale, int dz_nostore, uint8_t* __restrict__ qout, int64_t q_stride,
                                                       const float* __restrict__ qscale, unsigned* __restrict__ amax, int qfmt,
-                                                      int rows, int D) {
+                                                      int rows, int D, int dres_every) {
   __shared__ float red[4][MAXCH * 64 * W > 1280 ? 1280 : MAXCH * 64 * W];  // one partial at a time
   __shared__ float qred[4];
   const float qs = Q8 ? *qscale : 1.f;
@@ -242,7 +244,10 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const uint16_t* __restrict_
       const int c = min(lane + 64 * i, nch - 1);
       qx[i].load(x + (int64_t)rr * x_stride + c * W);
       qd[i].load(dy + (int64_t)rr * dy_stride + c * W);
-      if (dres)
+      if constexpr (SP) {
+        qr[i].load(dres + (int64_t)(rr / dres_every) * dres_stride + c * W);
+        if (rr % dres_every) qr[i].zero();  // wave-uniform
+      } else if (dres)
         qr[i].load(dres + (int64_t)rr * dres_stride + c * W);
       else
         qr[i].zero();
@@ -464,6 +469,9 @@ extern "C" hipError_t pvr_layernorm_bwd(const pvr::LnBwdParams* pp, hipStream_t 
   if (D % 8 != 0 || D > 1280 || (p.dz && (!d.seed || !d.thr))) return hipErrorInvalidValue;
   if (q.out && (!q.scale || !q.amax || q.ld % 8 != 0 || reinterpret_cast<uintptr_t>(q.out) % 8 != 0)) return hipErrorInvalidValue;
   if (p.dz_nostore && (!p.dz || !q.out)) return hipErrorInvalidValue;  // skipping dz needs dz's fp8 copy
+  // residual gradient on every dres_every-th row only (compact dres): the bf16 kernels
+  const bool sparse = p.dres && p.dres_every > 1;
+  if (p.dres_every < 0 || (sparse && q.out)) return hipErrorInvalidValue;
   // 4-column chunks (D = 768, profiles/r2s/ln_bwd_w4_ab.log): 79 -> 64 us per call (91 -> 79 with the
   // linked dropout backward); forcing 4 waves/SIMD (<= 128 VGPRs) spilled 18 VGPRs and took 114 us.
   // 4-column chunks when they tile the row over the 64 lanes exactly and 8-column ones do not
@@ -475,9 +483,9 @@ extern "C" hipError_t pvr_layernorm_bwd(const pvr::LnBwdParams* pp, hipStream_t 
   float* part = p.dw || p.db || p.dsum ? p.part : nullptr;
   const dim3 grid(nblk), block(256);
 #define PVR_LN_BWD(MC, W)                                                                                                   \
-  hipLaunchKernelGGL(q.out ? (ln_bwd_kernel<MC, W, true>) : (ln_bwd_kernel<MC, W, false>), grid, block, 0, s, p.dy, p.dy_stride, p.x, p.x_stride, p.mean, p.rstd, p.w, p.dres, p.dres_stride, p.dx, \
+  hipLaunchKernelGGL(q.out ? (ln_bwd_kernel<MC, W, true, false>) : sparse ? (ln_bwd_kernel<MC, W, false, true>) : (ln_bwd_kernel<MC, W, false, false>), grid, block, 0, s, p.dy, p.dy_stride, p.x, p.x_stride, p.mean, p.rstd, p.w, p.dres, p.dres_stride, p.dx, \
                      p.dx_stride, p.dw, p.db, p.dsum, part, p.dz, p.dz_stride, d.seed, d.offset, d.thr, d.scale, p.dz_nostore, q.out, q.ld, q.scale, q.amax, \
-                     q.fmt, rows, D)
+                     q.fmt, rows, D, p.dres_every)
   if (use_w4) {
     switch (D / 256) {
       case 3: PVR_LN_BWD(3, 4); break;  // D = 768

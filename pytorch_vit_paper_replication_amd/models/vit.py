@@ -306,16 +306,20 @@ class ViT(nn.Module):
     def _forward_fused(self, x: torch.Tensor, pre=None) -> torch.Tensor:
         from ..ops.fused_vit import HeadFn
 
-        tokens, store, B, N = self._fused_encoder(x, pre)
+        # the head reads token 0 only: the last block may return the class-token rows alone ([B, D])
+        tokens, store, B, N = self._fused_encoder(x, pre, cls_rows=True)
         head = self.classifier[0]
-        return HeadFn.apply(tokens, B, N, self.layer_norm.eps, store, self.layer_norm.weight, self.layer_norm.bias,
+        return HeadFn.apply(tokens, B, N if tokens.shape[0] == B * N else 1, self.layer_norm.eps, store, self.layer_norm.weight, self.layer_norm.bias,
                             head.weight, head.bias)
 
-    def _fused_encoder(self, x: torch.Tensor, pre=None):
+    def _fused_encoder(self, x: torch.Tensor, pre=None, cls_rows: bool = False):
         """Patch embedding + every encoder block on the fused path: (bf16 tokens [B*N, D], store, B, N).
         Shared by this model's head and the classifier-free backbone (models/vit_no_classifier.py).
+        ``cls_rows`` (a caller that reads token 0 of each image only): the last block may run on the
+        class-token rows alone (ops/fused_vit.py ``CLS_LAST_BLOCK``), and ``tokens`` is then ``[B, D]``.
         ``pre`` = ``(mean, std, geom)`` of a uint8 batch (:meth:`_device_input`), None for a float one."""
-        from ..ops.fused_vit import ATTN_SITE, EncoderBlockFn, block_links, PatchEmbedFn, PatchEmbedU8Fn, site_drop
+        from ..ops.fused_vit import (ATTN_SITE, EncoderBlockClsFn, EncoderBlockFn, PatchEmbedFn, PatchEmbedU8Fn, block_links,
+                                     cls_last_block_ok, site_drop)
         from ..runtime.param_store import get_store
 
         c = self.config
@@ -361,6 +365,10 @@ class ViT(nn.Module):
             mha = blk.msa_block.multi_head_attention
             drops = (site_drop(seed, 1 + 2 * i, blk.mlp_block.mlp[2].p, training), drops2[i],
                      site_drop(seed, ATTN_SITE + i, mha.dropout, training))
+            if cls_rows and i == len(blocks) - 1 and cls_last_block_ok(N, mha.num_heads, c["embedding_dim"], f8, drops[2]):
+                tokens = EncoderBlockClsFn.apply(tokens, B, N, mha.num_heads, ln1.eps, ln2.eps, store, drops, links[i],
+                                                 *blk.fused_params())
+                break
             tokens = EncoderBlockFn.apply(tokens, B, N, mha.num_heads, ln1.eps, ln2.eps, store, drops,
                                           None if f8 is None else (f8, i), links[i], *blk.fused_params())
         return tokens, store, B, N

@@ -479,10 +479,131 @@ class EncoderBlockFn(torch.autograd.Function):
         return (dx,) + (None,) * (9 + len(params))
 
 
+# The classifier reads token 0 of each image only, and after the last block's attention every
+# operation is row-wise: with this switch on (default) ViT._forward_fused runs the last encoder block
+# through EncoderBlockClsFn, which computes everything after the qkv GEMM for the B class-token rows
+# alone. False selects the full last block (A/Bs, parity tests).
+CLS_LAST_BLOCK = True
+
+
+def cls_last_block_ok(N: int, H: int, D: int, f8, dropa) -> bool:
+    """True if the last block of a classifier may run on its class-token rows: bf16 path (the fp8
+    delayed-scaling statistics cover every token), no attention dropout in this step, a shape the
+    class-token attention kernels take."""
+    return (CLS_LAST_BLOCK and f8 is None and gemm._drop_args(dropa)[0] is None
+            and D % H == 0 and bool(_ext.ext().attn_cls_ok(N, D // H)))
+
+
+class EncoderBlockClsFn(torch.autograd.Function):
+    """The last encoder block of a classifier: ``x [B*N, D]`` -> the block's output on the class-token
+    rows only, ``[B, D]``. LN1 and the qkv GEMM (and, backward, the qkv dgrad / weight gradient and the
+    LN1 backward) run on every token, since every token's K and V feed the class-token query; the
+    attention (csrc/attention.hip attn_cls_*), out-projection, LN2 and the MLP run on B rows. Dropout
+    masks are those of rows ``b * N`` of the full tensors, bit for bit (``drop_row_mul``). bf16 only,
+    no attention dropout (``cls_last_block_ok``)."""
+
+    @staticmethod
+    def forward(ctx, x, B, N, H, eps1, eps2, store, drops, links, *params):
+        ext = _ext.ext()
+        drop1, drop2, _ = drops
+        ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, w1, b1, w2, b2 = params
+        T, D = x.shape
+        ctx.links = links if links is not None else (None, None)
+        M = w1.shape[0]
+        scale = 1.0 / math.sqrt(D // H)
+        need_bwd = getattr(store, "grad_enabled", True) and any(ctx.needs_input_grad)
+        xn1, mean1, rstd1 = ext.layernorm_fwd(x, ln1w, ln1b, eps1, T, D)
+        qkv = gemm.linear_fwd(xn1, store.bf16(wqkv), bqkv)
+        o, lse = ext.attn_cls_fwd(qkv, B, N, H, scale)
+        xc = x.view(B, N, D)[:, 0]  # the class-token rows, in place (row stride N * D)
+        x1 = gemm.linear_fwd(o, store.bf16(wo), bo, resid=xc)
+        xn2, mean2, rstd2 = ext.layernorm_fwd(x1, ln2w, ln2b, eps2, B, D)
+        u = torch.empty(B, M, dtype=torch.bfloat16, device=x.device) if need_bwd else None
+        h = gemm.linear_fwd(xn2, store.bf16(w1), b1, gelu_aux=u, gelu=True, drop=drop1, drop_row_mul=N)
+        x2 = gemm.linear_fwd(h, store.bf16(w2), b2, resid=x1, drop=drop2, drop_row_mul=N)
+        if need_bwd:
+            ctx.save_for_backward(x, xn1, mean1, rstd1, qkv, o, lse, x1, xn2, mean2, rstd2, u, h)
+        ctx.meta = (B, N, H, scale, store, drop2, params)
+        return x2
+
+    @staticmethod
+    def backward(ctx, dx2):
+        ext = _ext.ext()
+        det = _ext.deterministic()  # native flag follows torch.use_deterministic_algorithms from this kernel on
+        x, xn1, mean1, rstd1, qkv, o, lse, x1, xn2, mean2, rstd2, u, h = ctx.saved_tensors
+        B, N, H, scale, store, drop2, params = ctx.meta
+        ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, w1, b1, w2, b2 = params
+        g = store.grad_dest
+        dx2 = dx2.contiguous()  # [B, D]: the gradient of the class-token rows
+        T, D = x.shape
+        _, prev = ctx.links
+
+        def dgrad(dy, w, which, dgelu_aux=None, colsum=None):
+            out = gemm.linear_dgrad(dy, store.bf16(w), dgelu_aux=dgelu_aux, wt=store.bf16_t(w), colsum=colsum)
+            if DGRAD_TAP is not None:
+                DGRAD_TAP(which, out)
+            return out
+
+        # ---- MLP branch on B rows (see EncoderBlockFn.backward)
+        if drop2 is not None:
+            dz2 = torch.empty_like(dx2)
+            gemm.bias_grad(dx2, g(b2), drop=drop2, dz=dz2, row_mul=N)
+        else:
+            dz2 = dx2
+            if b2.requires_grad:
+                gemm.bias_grad(dx2, g(b2))
+        gb1 = g(b1)
+        gw2, gw1 = g(w2), g(w1)
+        du = dgrad(dz2, w2, 0, dgelu_aux=u, colsum=None if det else gb1)
+        if det and gb1 is not None:
+            gemm.bias_grad(du, gb1)
+
+        def mlp_wgrads():  # reductions over B tokens
+            if gw2 is not None:
+                gemm.linear_wgrad(dz2, h, gw2)
+            if gw1 is not None:
+                gemm.linear_wgrad(du, xn2, gw1)
+
+        store.on_side(mlp_wgrads, dz2, h, du, xn2)
+        dxn2 = dgrad(du, w1, 1)
+        dx1 = torch.empty_like(dx2)
+        ext.layernorm_bwd(dxn2, D, x1, D, mean2, rstd2, ln2w, dx2, D, dx1, D, g(ln2w), g(ln2b), B, dsum=g(bo))
+        store.grad_ready([w2, b2, w1, b1, ln2w, ln2b])
+        # ---- attention branch: the class-token query against every token's K and V
+        gwo, gwqkv, gbqkv = g(wo), g(wqkv), g(bqkv)
+        do = dgrad(dx1, wo, 2)
+        dqkv, dq0 = ext.attn_cls_bwd(do, qkv, o, lse, B, N, H, scale)
+
+        def attn_wgrads():
+            if gbqkv is not None:
+                ext.attn_cls_dbias(dq0, do, gbqkv.view(-1))
+            if gwo is not None:
+                gemm.linear_wgrad(dx1, o, gwo)
+            if gwqkv is not None:
+                gemm.linear_wgrad(dqkv, xn1, gwqkv)
+
+        store.on_side(attn_wgrads, dx1, o, dqkv, xn1, do, dq0)
+        dxn1 = dgrad(dqkv, wqkv, 3)
+        dx = torch.empty_like(x)
+        # dx = LN1'(dxn1) on every row + dx1 on the class-token rows (compact: no zero-filled carrier)
+        if prev is not None:
+            # the previous block's fc2 dropout backward and bias gradient ride along with dx
+            seed, soff, p = gemm._drop_args(prev.drop2)
+            dzp = torch.empty_like(x) if seed is not None else None
+            ext.layernorm_bwd(dxn1, D, x, D, mean1, rstd1, ln1w, dx1, D, dx, D, g(ln1w), g(ln1b), T,
+                              dsum=g(prev.b2), dz=dzp, seed=seed, seed_offset=soff, drop_p=p, dres_every=N)
+            prev.dz2, prev.dz2_q, prev.done = dzp, None, True
+        else:
+            ext.layernorm_bwd(dxn1, D, x, D, mean1, rstd1, ln1w, dx1, D, dx, D, g(ln1w), g(ln1b), T, dres_every=N)
+        store.grad_ready([bo, wo, bqkv, wqkv, ln1w, ln1b])
+        return (dx,) + (None,) * (8 + len(params))
+
+
 class HeadFn(torch.autograd.Function):
     """Final LayerNorm (token 0 only) + classifier Linear in fp32 (csrc/head.hip: one forward launch;
     backward: dW / db / dgamma / dbeta and d(LN input) in two launches that also zero the other token
-    rows of the returned gradient)."""
+    rows of the returned gradient). ``N`` = 1: ``tokens`` holds the class-token rows alone ``[B, D]``
+    (EncoderBlockClsFn), and so does the returned gradient: nothing to zero."""
 
     @staticmethod
     def forward(ctx, tokens, B, N, eps, store, ln_w, ln_b, head_w, head_b):

@@ -107,8 +107,8 @@ def _small_splitk(T: int, N: int, K: int) -> int:
 DGRAD_TAIL_UNITS = 64
 
 
-def _gemm(*args, tile: int, colsum=None, tail_limit: int = 0):
-    _ext.ext().gemm(*args, tile, colsum=colsum, tail_limit=tail_limit)
+def _gemm(*args, tile: int, colsum=None, tail_limit: int = 0, drop_row_mul: int = 0):
+    _ext.ext().gemm(*args, tile, colsum=colsum, tail_limit=tail_limit, drop_row_mul=drop_row_mul)
 
 
 def _drop_args(drop: Drop):
@@ -121,8 +121,13 @@ def linear_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = 
                resid: Optional[torch.Tensor] = None, drop: Drop = None, gelu_aux: Optional[torch.Tensor] = None,
                gelu: bool = False,
                addend: Optional[torch.Tensor] = None, addend_period: int = 0,
-               row_remap: Tuple[int, int, int] = (0, 0, 0), out: Optional[torch.Tensor] = None) -> torch.Tensor:
+               row_remap: Tuple[int, int, int] = (0, 0, 0), out: Optional[torch.Tensor] = None,
+               drop_row_mul: int = 0) -> torch.Tensor:
     """y = resid + dropout(x.w^T + bias + addend[row % period]).
+
+    ``drop_row_mul`` = n > 1: the rows of ``x`` are a compact copy of every n-th row of a ``[T * n, K]``
+    token matrix (its class-token rows); row m draws the dropout mask of row ``m * n`` of the full
+    ``[T * n, N]`` output, bit for bit (the 128x128 tiles' epilogue).
 
     GELU variant (``gelu_aux`` given): u = x.w^T + bias, y = dropout(gelu(u)) and gelu_aux receives
     mask * scale * gelu'(u) — exactly the factor ``linear_dgrad(..., dgelu_aux=)`` multiplies by.
@@ -133,6 +138,12 @@ def linear_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = 
         out = torch.empty(T, N, dtype=torch.bfloat16, device=x.device)
     seed, soff, p = _drop_args(drop)
     epi = EPI_GELU if (gelu or gelu_aux is not None) else EPI_BF16
+    if drop_row_mul > 1 and p > 0.0:
+        if addend is not None or row_remap[0]:
+            raise ValueError("drop_row_mul does not combine with addend / row_remap")
+        _gemm(x, True, w, True, out, T, N, K, epi, bias, resid, None, 0, gelu_aux, 0, 0, 0, seed, soff, p, 0,
+              tile=0, drop_row_mul=int(drop_row_mul))
+        return out
     S = _small_splitk(T, N, K) if (p == 0.0 and gelu_aux is None and addend is None and row_remap[0] == 0) else 0
     if S:
         # serving-size batch: split K over workgroups (fp32 partials, tile 14), then one pass sums
@@ -281,8 +292,11 @@ def linear_wgrad(dy: torch.Tensor, x: torch.Tensor, out: torch.Tensor) -> torch.
 
 
 def bias_grad(dy: torch.Tensor, db: Optional[torch.Tensor], *, drop: Drop = None,
-              dz: Optional[torch.Tensor] = None, quant=None):
+              dz: Optional[torch.Tensor] = None, quant=None, row_mul: int = 1):
     """db += column sums of (mask * dy); writes the masked gradient to dz when given.
+
+    ``row_mul`` = n > 1: ``dy`` holds every n-th row of a ``[T * n, N]`` gradient (the class-token
+    rows, compact); row m takes the mask of row ``m * n`` there.
 
     ``quant=(meta, slot)`` (a calibrated gradient slot, ``Fp8Meta.producer``): the same pass writes the
     (masked) gradient's fp8 copy in the slot's format with the slot's delayed scale and records its amax; returns
@@ -290,10 +304,10 @@ def bias_grad(dy: torch.Tensor, db: Optional[torch.Tensor], *, drop: Drop = None
     T, N = dy.shape
     seed, soff, p = _drop_args(drop)
     if quant is None:
-        _ext.ext().colsum(dy, T, N, db, dz, seed, soff, p)
+        _ext.ext().colsum(dy, T, N, db, dz, seed, soff, p, row_mul=int(row_mul))
         return None
     meta, slot = quant
     q = torch.empty(T, N, dtype=torch.uint8, device=dy.device)
     _ext.ext().colsum(dy, T, N, db, dz, seed, soff, p, q_out=q, q_scale=meta.qscale[slot:slot + 1],
-                      q_amax=meta.amax[slot:slot + 1], q_fmt=meta.fmt)
+                      q_amax=meta.amax[slot:slot + 1], q_fmt=meta.fmt, row_mul=int(row_mul))
     return q, meta.dscale[slot:slot + 1]
