@@ -62,7 +62,24 @@ def build_parser():
                    help="with --device-preprocess: random-resized-crop + horizontal flip on the device in training")
     p.add_argument("--source-size", type=int, default=None,
                    help="with --device-preprocess: side of the uint8 images the loader yields (default: --image-size)")
+    p.add_argument("--mixup", type=float, default=0.0, metavar="A", help="mixup with lam ~ Beta(A, A) (0: off)")
+    p.add_argument("--cutmix", type=float, default=0.0, metavar="A", help="CutMix with lam ~ Beta(A, A) (0: off)")
+    p.add_argument("--mix-prob", type=float, default=1.0, help="probability that a batch is mixed")
+    p.add_argument("--mix-switch-prob", type=float, default=0.5, help="with both: probability of CutMix over mixup")
+    p.add_argument("--label-smoothing", type=float, default=0.0, metavar="E", help="label smoothing of the loss (0: off)")
     return p
+
+
+def build_batch_mix(args, rank: int = 0):
+    """The :class:`~..data.batch_mix.BatchMix` of ``--mixup`` / ``--cutmix`` (None when both are off: label
+    smoothing alone goes into the loss function), its generator seeded from ``--seed`` per rank."""
+    if args.mixup <= 0 and args.cutmix <= 0:
+        return None
+    from ..data.batch_mix import BatchMix
+
+    gen = torch.Generator().manual_seed(args.seed * 1_000_003 + 7919 + rank)
+    return BatchMix(mixup_alpha=args.mixup, cutmix_alpha=args.cutmix, prob=args.mix_prob, switch_prob=args.mix_switch_prob,
+                    label_smoothing=args.label_smoothing, generator=gen)
 
 
 def main(argv=None) -> int:
@@ -127,9 +144,10 @@ def main(argv=None) -> int:
            if is_dist() else model)
     with _ext.deterministic_mode() if args.deterministic else contextlib.nullcontext():
         engine.train(model=net, train_dataloader=train_dl, test_dataloader=test_dl, optimizer=opt,
-                     loss_fn=torch.nn.CrossEntropyLoss(), lr_scheduler=sched, epochs=args.epochs, device=device,
-                     max_grad_norm=args.max_grad_norm, checkpoint_dir=args.checkpoint_dir, metrics_path=args.metrics,
-                     start_epoch=start_epoch, results=results)
+                     loss_fn=torch.nn.CrossEntropyLoss(label_smoothing=args.label_smoothing), lr_scheduler=sched,
+                     epochs=args.epochs, device=device, max_grad_norm=args.max_grad_norm, checkpoint_dir=args.checkpoint_dir,
+                     metrics_path=args.metrics, start_epoch=start_epoch, results=results,
+                     batch_mix=build_batch_mix(args, rank))
     save_model(model, args.save_dir, args.save_name or f"{args.model}_{args.epochs}_epochs.pth")
     return 0
 

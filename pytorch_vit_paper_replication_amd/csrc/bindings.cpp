@@ -414,10 +414,55 @@ void colsum(torch::Tensor dy, int64_t rows, int64_t N, c10::optional<torch::Tens
         "colsum");
 }
 
-void im2col(torch::Tensor img, torch::Tensor out, int64_t P, int64_t Kp) {
+// A batch-mix plan for the patchify kernels (csrc/kernels.h MixRow): `mix` int32 [B, 8] on the image's
+// device, validated here on the host so that no kernel ever sees a partner outside [0, B) or a box
+// outside the H x W output. `host` is the CPU tensor the device copy was uploaded from (MixPlan keeps
+// it); without it the device tensor is read back, which synchronises.
+const pvr::MixRow* mix_rows(const c10::optional<torch::Tensor>& mix, const c10::optional<torch::Tensor>& host, int64_t B, int64_t H,
+                            int64_t W, const torch::Tensor& img, const char* what) {
+  if (!mix.has_value() || !mix->defined()) {
+    TORCH_CHECK(!host.has_value() || !host->defined(), what, ": mix_host without mix");
+    return nullptr;
+  }
+  TORCH_CHECK(mix->is_cuda() && mix->device() == img.device(), what, ": mix must be on the image's device");
+  TORCH_CHECK(mix->scalar_type() == torch::kInt32 && mix->dim() == 2 && mix->size(0) == B && mix->size(1) == 8 && mix->is_contiguous(),
+              what, ": mix must be contiguous int32 [", B, ", 8]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(mix->data_ptr()) % 16 == 0, what, ": mix must be 16-byte aligned");
+  torch::Tensor h;
+  if (host.has_value() && host->defined()) {
+    TORCH_CHECK(!host->is_cuda() && host->scalar_type() == torch::kInt32 && host->dim() == 2 && host->size(0) == B &&
+                    host->size(1) == 8 && host->is_contiguous(),
+                what, ": mix_host must be a contiguous CPU int32 [", B, ", 8] tensor");
+    h = *host;
+  } else {
+    h = mix->cpu();
+  }
+  const auto* rows = reinterpret_cast<const pvr::MixRow*>(h.data_ptr());
+  for (int64_t b = 0; b < B; ++b) {
+    const pvr::MixRow& r = rows[b];
+    TORCH_CHECK(r.partner >= 0 && r.partner < B, what, ": mix row ", b, " has partner ", r.partner, " outside [0, ", B, ")");
+    TORCH_CHECK(r.lam >= 0.f && r.lam <= 1.f, what, ": mix row ", b, " has lam ", r.lam, " outside [0, 1]");
+    TORCH_CHECK(r.bx0 >= 0 && r.bx0 <= r.bx1 && r.bx1 <= W && r.by0 >= 0 && r.by0 <= r.by1 && r.by1 <= H, what, ": mix row ", b,
+                " has box (", r.bx0, ", ", r.by0, ", ", r.bx1, ", ", r.by1, ") outside the ", H, "x", W, " image");
+  }
+  return reinterpret_cast<const pvr::MixRow*>(mix->data_ptr());
+}
+
+void im2col(torch::Tensor img, torch::Tensor out, int64_t P, int64_t Kp, c10::optional<torch::Tensor> mix,
+            c10::optional<torch::Tensor> mix_host) {
   TORCH_CHECK(img.is_contiguous() && img.dim() == 4, "im2col: img must be contiguous NCHW");
+  const pvr::MixRow* mp = mix_rows(mix, mix_host, img.size(0), img.size(2), img.size(3), img, "im2col");
+  if (mp) {  // the plain call keeps its checks; a plan adds those that keep the second read in bounds
+    const int64_t rows = P > 0 ? img.size(0) * (img.size(2) / P) * (img.size(3) / P) : -1;
+    TORCH_CHECK(img.is_cuda() && P > 0 && img.size(2) % P == 0 && img.size(3) % P == 0 && Kp % 8 == 0 &&
+                    Kp >= img.size(1) * P * P,
+                "im2col: the image must be a GPU tensor whose sides are multiples of the patch size, Kp a multiple of 8 >= C*P*P");
+    TORCH_CHECK(out.is_cuda() && out.device() == img.device() && out.is_contiguous() && out.dim() == 2 && out.size(0) == rows &&
+                    out.size(1) == Kp,
+                "im2col: out must be contiguous bf16 [", rows, ", ", Kp, "] on the image's device");
+  }
   check(pvr_im2col(f32(img, "img"), bf_mut(out, "out"), (int)img.size(0), (int)img.size(1), (int)img.size(2), (int)img.size(3),
-                   (int)P, (int)Kp, stream()),
+                   (int)P, (int)Kp, mp, stream()),
         "im2col");
 }
 
@@ -426,7 +471,8 @@ void im2col(torch::Tensor img, torch::Tensor out, int64_t P, int64_t Kp) {
 // cropped / resized / flipped per sample (csrc/elementwise.hip im2col_u8_kernel). Returns 1 when
 // the 8-byte-load path ran, 0 for the per-element path (decided here from data_ptr and strides).
 int64_t im2col_u8(torch::Tensor img, torch::Tensor out, std::vector<double> mean, std::vector<double> stdv,
-                  c10::optional<torch::Tensor> geom, int64_t H, int64_t W, int64_t P, int64_t Kp) {
+                  c10::optional<torch::Tensor> geom, int64_t H, int64_t W, int64_t P, int64_t Kp, c10::optional<torch::Tensor> mix,
+                  c10::optional<torch::Tensor> mix_host) {
   TORCH_CHECK(img.is_cuda() && img.scalar_type() == torch::kUInt8, "im2col_u8: img must be a uint8 GPU tensor, got ",
               img.scalar_type(), " on ", img.device());
   TORCH_CHECK(img.dim() == 4, "im2col_u8: img must be [B, C, Hs, Ws], got ", img.dim(), " dims");
@@ -454,6 +500,7 @@ int64_t im2col_u8(torch::Tensor img, torch::Tensor out, std::vector<double> mean
   } else {
     TORCH_CHECK(Hs == H && Ws == W, "im2col_u8: a ", Hs, "x", Ws, " source needs geom to produce ", H, "x", W);
   }
+  const pvr::MixRow* mp = mix_rows(mix, mix_host, B, H, W, img, "im2col_u8");
   const int64_t sb = img.stride(0), sc = img.stride(1), sy = img.stride(2), sx = img.stride(3);
   TORCH_CHECK(sb >= 0 && sc >= 0 && sy >= 0 && sx >= 0, "im2col_u8: negative strides");
   const uint8_t* ip = img.data_ptr<uint8_t>();
@@ -464,9 +511,37 @@ int64_t im2col_u8(torch::Tensor img, torch::Tensor out, std::vector<double> mean
     sd[c] = (float)stdv[c];
   }
   check(pvr_im2col_u8(ip, sb, sc, sy, sx, m, sd, gp, bf_mut(out, "out"), (int)B, (int)C, (int)Hs, (int)Ws, (int)H, (int)W, (int)P,
-                      (int)Kp, vec, stream()),
+                      (int)Kp, vec, mp, stream()),
         "im2col_u8");
   return vec;
+}
+
+// xent for soft target rows (mixed label pairs ya / yb with per-row weight lam, label smoothing eps;
+// csrc/xent.hip xent_soft_kernel): same outputs as xent, `correct` against ya
+torch::Tensor xent_soft(torch::Tensor logits, torch::Tensor ya, torch::Tensor yb, torch::Tensor lam, double eps,
+                        c10::optional<torch::Tensor> dlogits, c10::optional<torch::Tensor> correct, double grad_scale,
+                        c10::optional<torch::Tensor> mean) {
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.size(1) >= 1, "xent_soft: logits must be [B, C] row-major");
+  const int64_t B = logits.size(0), C = logits.size(1);
+  for (const torch::Tensor* y : {&ya, &yb})
+    TORCH_CHECK(y->is_cuda() && y->device() == logits.device() && y->scalar_type() == torch::kInt64 && y->is_contiguous() &&
+                    y->numel() == B,
+                "xent_soft: ya / yb must be contiguous int64 [B] on the logits' device");
+  TORCH_CHECK(lam.device() == logits.device() && lam.is_contiguous() && lam.numel() == B, "xent_soft: lam must be contiguous float32 [B]");
+  TORCH_CHECK(eps >= 0.0 && eps <= 1.0, "xent_soft: eps must be in [0, 1], got ", eps);
+  if (correct.has_value() && correct->defined())
+    TORCH_CHECK(correct->is_cuda() && correct->numel() >= B && correct->scalar_type() == torch::kInt32, "xent_soft: correct int32 [B]");
+  if (dlogits.has_value() && dlogits->defined())
+    TORCH_CHECK(dlogits->is_cuda() && dlogits->is_contiguous() && dlogits->numel() == B * C && dlogits->scalar_type() == torch::kFloat32,
+                "xent_soft: dlogits f32 [B][C]");
+  if (mean.has_value() && mean->defined()) TORCH_CHECK(mean->numel() >= 1, "xent_soft: mean [1]");
+  auto loss = torch::empty({B}, logits.options().dtype(torch::kFloat32));
+  check(pvr_xent_soft(f32(logits, "logits"), logits.stride(0), ya.data_ptr<int64_t>(), yb.data_ptr<int64_t>(), f32(lam, "lam"),
+                      (float)eps, (int)B, (int)C, loss.data_ptr<float>(), opt_ptr<float>(dlogits), opt_ptr<int>(correct),
+                      (float)grad_scale, stream()),
+        "xent_soft");
+  if (mean.has_value() && mean->defined()) check(pvr_mean(loss.data_ptr<float>(), (int)B, f32_mut(*mean, "mean"), stream()), "xent_soft mean");
+  return loss;
 }
 
 void cls_rows(torch::Tensor cls, torch::Tensor pos, torch::Tensor out, int64_t B, int64_t D, int64_t row_stride,
@@ -1097,13 +1172,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("colsum", &colsum, py::arg("dy"), py::arg("rows"), py::arg("N"), py::arg("db"), py::arg("dz"), py::arg("seed"),
         py::arg("seed_offset"), py::arg("drop_p"), py::arg("q_out") = py::none(), py::arg("q_scale") = py::none(),
         py::arg("q_amax") = py::none(), py::arg("q_fmt") = 1, py::arg("row_mul") = 1);
-  m.def("im2col", &im2col);
+  m.def("im2col", &im2col, py::arg("img"), py::arg("out"), py::arg("P"), py::arg("Kp"), py::arg("mix") = py::none(),
+        py::arg("mix_host") = py::none());
   m.def("im2col_u8", &im2col_u8, py::arg("img"), py::arg("out"), py::arg("mean"), py::arg("std"), py::arg("geom"), py::arg("H"),
-        py::arg("W"), py::arg("P"), py::arg("Kp"));
+        py::arg("W"), py::arg("P"), py::arg("Kp"), py::arg("mix") = py::none(), py::arg("mix_host") = py::none());
   m.def("cls_rows", &cls_rows);
   m.def("patch_bwd", &patch_bwd);
   m.def("xent", &xent, py::arg("logits"), py::arg("labels"), py::arg("dlogits"), py::arg("correct"), py::arg("grad_scale"),
         py::arg("mean") = py::none());
+  m.def("xent_soft", &xent_soft, py::arg("logits"), py::arg("ya"), py::arg("yb"), py::arg("lam"), py::arg("eps"),
+        py::arg("dlogits"), py::arg("correct"), py::arg("grad_scale"), py::arg("mean") = py::none());
   m.def("grad_norm", &grad_norm);
   m.def("norm_partial_blocks", []() { return pvr_norm_partial_blocks(); });
   m.def("adam", &adam);

@@ -112,12 +112,34 @@ __global__ void __launch_bounds__(256) colsum_kernel(const uint16_t* __restrict_
   }
 }
 
+// One mixed pixel of the patchify kernels' MIX variants (MixRow in kernels.h): fp32, contraction off
+PVR_DEV float mix_value(float own, float par, bool inside, float lam, float oml) {
+#pragma clang fp contract(off)
+  return inside ? par : lam == 1.f ? own : lam * own + oml * par;
+}
+
+// mix[b] with the partner index made safe to use (the host validates the plan it was given; a device
+// tensor that differs from it must still never index outside the batch)
+PVR_DEV MixRow mix_row(const MixRow* __restrict__ mix, int b, int B) {
+  const int4 lo = ((const int4*)(mix + b))[0], hi = ((const int4*)(mix + b))[1];
+  MixRow r;
+  r.partner = (unsigned)lo.x < (unsigned)B ? lo.x : b;
+  r.lam = __int_as_float(lo.y);
+  r.bx0 = lo.z; r.by0 = lo.w; r.bx1 = hi.x; r.by1 = hi.y;
+  return r;
+}
+
 // img [B][C][H][W] fp32 -> patches [B*np][Kp] bf16, k = (c*P + ph)*P + pw, zero padded to Kp.
 // One thread per 8 consecutive k of a patch row: with P % 8 == 0 they are 8 consecutive pixels of
 // one image row (two float4 loads, one 16-B store); the zero padding past C*P*P and other patch
 // sizes (P = 14) take the per-element path.
+// MIX: sample b's pixels are blended with / replaced by those of sample mix[b].partner while they
+// are gathered (mixup / CutMix, see MixRow in kernels.h). A pixel whose weight is 0 or 1 is read from
+// one sample only, so CutMix moves the bytes of the plain gather; mixup reads the input twice.
+template <bool MIX>
 __global__ void __launch_bounds__(256) im2col_kernel(const float* __restrict__ img, uint16_t* __restrict__ out,
-                                                      int B, int C, int H, int W, int P, int Kp) {
+                                                      int B, int C, int H, int W, int P, int Kp,
+                                                      const MixRow* __restrict__ mix) {
   const int gw = W / P, np = (H / P) * gw;
   const int kc = C * P * P, k8 = Kp / 8;
   const bool vec = (P % 8 == 0) && (W % 4 == 0);
@@ -129,7 +151,52 @@ __global__ void __launch_bounds__(256) im2col_kernel(const float* __restrict__ i
     const int b = (int)(rowi / np);
     const int y0 = (pidx / gw) * P, x0 = (pidx % gw) * P;
     float v[8];
-    if (vec && k0 + 8 <= kc) {
+    if constexpr (MIX) {
+      const MixRow r = mix_row(mix, b, B);
+      const float oml = 1.0f - r.lam;
+      if (vec && k0 + 8 <= kc) {
+        const int c = k0 / (P * P), rem = k0 % (P * P), ph = rem / P, pw = rem % P;
+        const int y = y0 + ph, x = x0 + pw;
+        const bool yin = y >= r.by0 && y < r.by1;
+        bool in[8];
+        int n_in = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          in[j] = yin && x + j >= r.bx0 && x + j < r.bx1;
+          n_in += in[j];
+        }
+        const int64_t off = ((int64_t)c * H + y) * W + x;
+        float4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, p0 = a0, p1 = a0;
+        if (n_in < 8) {
+          const float* src = img + (int64_t)b * C * H * W + off;
+          a0 = *(const float4*)src; a1 = *(const float4*)(src + 4);
+        }
+        if (n_in > 0 || r.lam != 1.f) {
+          const float* src = img + (int64_t)r.partner * C * H * W + off;
+          p0 = *(const float4*)src; p1 = *(const float4*)(src + 4);
+        }
+        const float a[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+        const float p[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = mix_value(a[j], p[j], in[j], r.lam, oml);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int k = k0 + j;
+          v[j] = 0.f;
+          if (k < kc) {
+            const int c = k / (P * P), rem = k % (P * P), ph = rem / P, pw = rem % P;
+            const int y = y0 + ph, x = x0 + pw;
+            const bool in = y >= r.by0 && y < r.by1 && x >= r.bx0 && x < r.bx1;
+            const int64_t off = ((int64_t)c * H + y) * W + x;
+            float a = 0.f, p = 0.f;
+            if (!in) a = img[(int64_t)b * C * H * W + off];
+            if (in || r.lam != 1.f) p = img[(int64_t)r.partner * C * H * W + off];
+            v[j] = mix_value(a, p, in, r.lam, oml);
+          }
+        }
+      }
+    } else if (vec && k0 + 8 <= kc) {
       const int c = k0 / (P * P), rem = k0 % (P * P), ph = rem / P, pw = rem % P;
       const float* src = img + (((int64_t)b * C + c) * H + y0 + ph) * W + x0 + pw;
       const float4 a = *(const float4*)src, bq = *(const float4*)(src + 4);
@@ -187,18 +254,41 @@ PVR_DEV void u8_axis(int o, float e0, float step, int n_src, int& i, int& j, flo
   w = s - f;
 }
 
-template <bool GEOM>
+// Output pixel (x, y) of one channel plane under crop box g (steps precomputed): the bilinear sample
+// of the four taps, normalised; fp32, before the bf16 cast. The GEOM loop body of im2col_u8_kernel as
+// a function, for its MIX variant, which samples two images per pixel (the no-mix kernel keeps the
+// body inline: calling this there schedules differently).
+PVR_DEV float u8_sample(const uint8_t* src_c, int64_t sy, int64_t sx, const float4& g, float stepx, float stepy, int x, int y,
+                        int Ws, int Hs, float mean, float stdv) {
+#pragma clang fp contract(off)
+  int xi, xj, yi, yj;
+  float wx, wy;
+  u8_axis(x, g.x, stepx, Ws, xi, xj, wx);
+  u8_axis(y, g.y, stepy, Hs, yi, yj, wy);
+  const float ta = (float)src_c[yi * sy + xi * sx], tb = (float)src_c[yi * sy + xj * sx];
+  const float tc = (float)src_c[yj * sy + xi * sx], td = (float)src_c[yj * sy + xj * sx];
+  const float top = ta + wx * (tb - ta), bot = tc + wx * (td - tc);
+  return u8_normalise(top + wy * (bot - top), mean, stdv);
+}
+
+// MIX (see im2col_kernel): the blend runs on the normalised fp32 values, each sample under its own
+// crop box, so the no-GEOM table then holds fp32 values instead of their bf16 roundings.
+template <bool GEOM, bool MIX>
 __global__ void __launch_bounds__(256) im2col_u8_kernel(const uint8_t* __restrict__ img, int64_t sb, int64_t sc, int64_t sy,
                                                          int64_t sx, U8Norm nrm, const float* __restrict__ geom,
                                                          uint16_t* __restrict__ out, int B, int C, int Hs, int Ws, int H, int W,
-                                                         int P, int Kp, int vec) {
+                                                         int P, int Kp, int vec, const MixRow* __restrict__ mix) {
 #pragma clang fp contract(off)
   // Without GEOM a pixel is one of 256 byte values: each block tabulates the normalised bf16 of every
   // (channel, byte) pair once, with the same operations and hence the same bits, and its loop does
   // no division. Two correctly rounded divisions per element make the kernel ALU-bound: 51 us
   // against 38 us with the table at 256 x 224 x 224 (the float kernel: 43 us), profiles/input_u8/.
-  __shared__ uint16_t lut[GEOM ? 1 : 4][256];
-  if constexpr (!GEOM) {
+  __shared__ uint16_t lut[GEOM || MIX ? 1 : 4][256];
+  __shared__ float lutf[!GEOM && MIX ? 4 : 1][256];
+  if constexpr (!GEOM && MIX) {
+    for (int c = 0; c < C; ++c) lutf[c][threadIdx.x] = u8_normalise((float)threadIdx.x, nrm.mean[c], nrm.stdv[c]);
+    __syncthreads();
+  } else if constexpr (!GEOM) {
     for (int c = 0; c < C; ++c) lut[c][threadIdx.x] = f2bf(u8_normalise((float)threadIdx.x, nrm.mean[c], nrm.stdv[c]));
     __syncthreads();
   }
@@ -213,7 +303,74 @@ __global__ void __launch_bounds__(256) im2col_u8_kernel(const uint8_t* __restric
     const int py = (pidx / gw) * P, px = (pidx % gw) * P;
     const uint8_t* src_b = img + b * sb;
     uint32_t h[8];  // bf16 bits
-    if constexpr (!GEOM) {
+    if constexpr (MIX) {
+      const MixRow r = mix_row(mix, b, B);
+      const float oml = 1.0f - r.lam;
+      const uint8_t* src_p = img + r.partner * sb;
+      float v[8];
+      if constexpr (!GEOM) {
+        if (vec && k0 + 8 <= kc) {
+          const int c = k0 / (P * P), rem = k0 % (P * P), ph = rem / P, pw = rem % P;
+          const int y = py + ph, x = px + pw;
+          const bool yin = y >= r.by0 && y < r.by1;
+          bool in[8];
+          int n_in = 0;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            in[j] = yin && x + j >= r.bx0 && x + j < r.bx1;
+            n_in += in[j];
+          }
+          const int64_t off = c * sc + (int64_t)y * sy + x;
+          uint2 qa = {0u, 0u}, qp = {0u, 0u};
+          if (n_in < 8) qa = *(const uint2*)(src_b + off);
+          if (n_in > 0 || r.lam != 1.f) qp = *(const uint2*)(src_p + off);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const uint32_t a = ((j < 4 ? qa.x : qa.y) >> (8 * (j & 3))) & 0xFFu;
+            const uint32_t p = ((j < 4 ? qp.x : qp.y) >> (8 * (j & 3))) & 0xFFu;
+            v[j] = mix_value(lutf[c][a], lutf[c][p], in[j], r.lam, oml);
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const int k = k0 + j;
+            v[j] = 0.f;
+            if (k < kc) {
+              const int c = k / (P * P), rem = k % (P * P), ph = rem / P, pw = rem % P;
+              const int y = py + ph, x = px + pw;
+              const bool in = y >= r.by0 && y < r.by1 && x >= r.bx0 && x < r.bx1;
+              const int64_t off = c * sc + (int64_t)y * sy + (int64_t)x * sx;
+              float a = 0.f, p = 0.f;
+              if (!in) a = lutf[c][src_b[off]];
+              if (in || r.lam != 1.f) p = lutf[c][src_p[off]];
+              v[j] = mix_value(a, p, in, r.lam, oml);
+            }
+          }
+        }
+      } else {
+        // each sample under its own crop box
+        const float4 g = *(const float4*)(geom + (int64_t)b * 4), gp = *(const float4*)(geom + (int64_t)r.partner * 4);
+        const float stepx = (g.z - g.x) / (float)W, stepy = (g.w - g.y) / (float)H;
+        const float pstepx = (gp.z - gp.x) / (float)W, pstepy = (gp.w - gp.y) / (float)H;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int k = k0 + j;
+          v[j] = 0.f;
+          if (k < kc) {
+            const int c = k / (P * P), rem = k % (P * P), ph = rem / P, pw = rem % P;
+            const int y = py + ph, x = px + pw;
+            const bool in = y >= r.by0 && y < r.by1 && x >= r.bx0 && x < r.bx1;
+            const float mean = pick4(nrm.mean, c), stdv = pick4(nrm.stdv, c);
+            float a = 0.f, p = 0.f;
+            if (!in) a = u8_sample(src_b + c * sc, sy, sx, g, stepx, stepy, x, y, Ws, Hs, mean, stdv);
+            if (in || r.lam != 1.f) p = u8_sample(src_p + c * sc, sy, sx, gp, pstepx, pstepy, x, y, Ws, Hs, mean, stdv);
+            v[j] = mix_value(a, p, in, r.lam, oml);
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) h[j] = f2bf(v[j]);
+    } else if constexpr (!GEOM) {
       if (vec && k0 + 8 <= kc) {
         const int c = k0 / (P * P), rem = k0 % (P * P), ph = rem / P, pw = rem % P;
         const uint2 q = *(const uint2*)(src_b + c * sc + (int64_t)(py + ph) * sy + px + pw);
@@ -593,21 +750,24 @@ extern "C" hipError_t pvr_colsum(const uint16_t* dy, int64_t ld, int rows, int N
   return pvr_rows_reduce(part, gy, N, N, db, nullptr, nullptr, s);
 }
 
-extern "C" hipError_t pvr_im2col(const float* img, uint16_t* out, int B, int C, int H, int W, int P, int Kp, hipStream_t s) {
+extern "C" hipError_t pvr_im2col(const float* img, uint16_t* out, int B, int C, int H, int W, int P, int Kp,
+                                 const pvr::MixRow* mix, hipStream_t s) {
   using namespace pvr;
-  if (Kp % 8) return hipErrorInvalidValue;
+  if (Kp % 8 || (mix && reinterpret_cast<uintptr_t>(mix) % 16)) return hipErrorInvalidValue;
   const int64_t total = (int64_t)B * (H / P) * (W / P) * (Kp / 8);
   if (total <= 0) return hipSuccess;
   int64_t blocks = (total + 255) / 256;
   if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(im2col_kernel, dim3((unsigned)blocks), dim3(256), 0, s, img, out, B, C, H, W, P, Kp);
+  hipLaunchKernelGGL(mix ? im2col_kernel<true> : im2col_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, img, out, B, C, H, W,
+                     P, Kp, mix);
   return hipGetLastError();
 }
 
 extern "C" hipError_t pvr_im2col_u8(const uint8_t* img, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float* mean,
                                     const float* stdv, const float* geom, uint16_t* out, int B, int C, int Hs, int Ws, int H,
-                                    int W, int P, int Kp, int vec, hipStream_t s) {
+                                    int W, int P, int Kp, int vec, const pvr::MixRow* mix, hipStream_t s) {
   using namespace pvr;
+  if (mix && reinterpret_cast<uintptr_t>(mix) % 16) return hipErrorInvalidValue;
   if (Kp % 8 || P <= 0 || C < 1 || C > 4 || H % P || W % P || Kp < C * P * P || Hs < 1 || Ws < 1) return hipErrorInvalidValue;
   if (!geom && (Hs != H || Ws != W)) return hipErrorInvalidValue;
   if (vec && (geom || sx != 1 || P % 8 || reinterpret_cast<uintptr_t>(img) % 8 || sb % 8 || sc % 8 || sy % 8))
@@ -621,8 +781,10 @@ extern "C" hipError_t pvr_im2col_u8(const uint8_t* img, int64_t sb, int64_t sc, 
     nrm.mean[c] = c < C ? mean[c] : 0.f;
     nrm.stdv[c] = c < C ? stdv[c] : 1.f;
   }
-  hipLaunchKernelGGL(geom ? im2col_u8_kernel<true> : im2col_u8_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, img, sb, sc,
-                     sy, sx, nrm, geom, out, B, C, Hs, Ws, H, W, P, Kp, vec);
+  const auto kern = mix ? (geom ? im2col_u8_kernel<true, true> : im2col_u8_kernel<false, true>)
+                        : (geom ? im2col_u8_kernel<true, false> : im2col_u8_kernel<false, false>);
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, s, img, sb, sc, sy, sx, nrm, geom, out, B, C, Hs, Ws, H, W, P, Kp,
+                     vec, mix);
   return hipGetLastError();
 }
 

@@ -33,6 +33,22 @@ struct Fp8Copy {
   uint8_t* out = nullptr; int64_t ld = 0; const float* scale = nullptr; unsigned* amax = nullptr; int fmt = 0;
 };
 
+// One sample's row of a batch-mix plan (mixup / CutMix in the patchify kernels), int32 [B][8] on the
+// device with lam's float bits in word 1 (data/batch_mix.py MixPlan); rows are 32 bytes, the base
+// 16-byte aligned. With pre(s, ...) the fp32 value a kernel produces for sample s before its bf16
+// cast, output pixel (b, c, y, x) becomes
+//   pre(partner, c, y, x)                                   inside the half-open box, bx0 <= x < bx1 and by0 <= y < by1
+//   pre(b, c, y, x)                                         else if lam == 1 (a select)
+//   lam * pre(b, ...) + (1.0f - lam) * pre(partner, ...)    otherwise (fp32, each operation rounded on its own)
+// Mixup: lam < 1, empty box. CutMix: lam == 1 and a box. Box coordinates are output (model image) pixels.
+struct MixRow {
+  int partner;  // in [0, B)
+  float lam;
+  int bx0, by0, bx1, by1;  // inside [0, W] x [0, H]
+  int pad[2];  // not read by the kernels (MixPlan keeps the label weight's float bits in pad[0])
+};
+static_assert(sizeof(MixRow) == 32, "MixRow is one int32 [8] row of the plan tensor");
+
 // pvr_layernorm_bwd: dx = dres + LN'(dy); dw / db / dsum (each optional) accumulate dgamma, dbeta
 // and the column sums of dx.
 struct LnBwdParams {
@@ -126,12 +142,14 @@ hipError_t pvr_colsum(const uint16_t* dy, int64_t ld, int rows, int N, float* db
                       pvr::Fp8Copy q, float* part, int row_mul, hipStream_t s);
 // d0/d1/d2[c % seg] += sum over the R rows of part[R][C] (row order: deterministic)
 hipError_t pvr_rows_reduce(const float* part, int R, int C, int seg, float* d0, float* d1, float* d2, hipStream_t s);
-hipError_t pvr_im2col(const float* img, uint16_t* out, int B, int C, int H, int W, int P, int Kp, hipStream_t s);
+// mix (both patchify kernels; null: none): the batch's MixRow plan, host-validated (bindings.cpp mix_rows)
+hipError_t pvr_im2col(const float* img, uint16_t* out, int B, int C, int H, int W, int P, int Kp, const pvr::MixRow* mix,
+                      hipStream_t s);
 // strides in elements (= bytes); geom null: Hs == H and Ws == W. `vec`: the caller has checked the
 // 8-byte load conditions on the base pointer and strides (bindings.cpp im2col_u8).
 hipError_t pvr_im2col_u8(const uint8_t* img, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float* mean, const float* stdv,
                          const float* geom, uint16_t* out, int B, int C, int Hs, int Ws, int H, int W, int P, int Kp, int vec,
-                         hipStream_t s);
+                         const pvr::MixRow* mix, hipStream_t s);
 hipError_t pvr_cls_rows(const float* cls, const float* pos, uint16_t* out, int B, int D, int64_t row_stride, pvr::DropSite drop,
                         hipStream_t s);
 hipError_t pvr_patch_bwd(const uint16_t* dE, int B, int ntok, int D, float* ws, float* dpos, float* dcls, uint16_t* dconv,
@@ -153,6 +171,12 @@ hipError_t pvr_rng_next(int64_t* rng, int64_t* seed, hipStream_t s);
 hipError_t pvr_zero_f32(float* x, int64_t n, hipStream_t s);
 hipError_t pvr_xent(const float* logits, int64_t ld, const int64_t* labels, int B, int C, float* loss_rows, float* dlogits,
                     int* correct, float grad_scale, hipStream_t s);
+// Soft-target rows q = (1 - eps) * (lam * onehot(ya) + (1 - lam) * onehot(yb)) + eps / C (mixed labels,
+// label smoothing): loss_rows = -sum_c q_c log softmax_c, dlogits = (softmax - q) * grad_scale,
+// correct = (argmax == ya). lam = 1, eps = 0, yb = ya gives pvr_xent's bits. A row whose ya or yb is
+// outside [0, C) has zero loss and gradient.
+hipError_t pvr_xent_soft(const float* logits, int64_t ld, const int64_t* ya, const int64_t* yb, const float* lam, float eps, int B,
+                         int C, float* loss_rows, float* dlogits, int* correct, float grad_scale, hipStream_t s);
 
 // ---- optim.hip
 int pvr_norm_partial_blocks();

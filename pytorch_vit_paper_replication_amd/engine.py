@@ -33,7 +33,7 @@ except Exception:  # pragma: no cover
 
 from .data.prefetch import prefetch
 from .ops import fused_vit
-from .ops.fused_vit import cross_entropy
+from .ops.fused_vit import cross_entropy, soft_cross_entropy
 from .utils.profiling import range_push
 
 
@@ -45,19 +45,45 @@ def _rank0() -> bool:
     return not _is_dist() or torch.distributed.get_rank() == 0
 
 
+class _SoftLoss:
+    """``soft_cross_entropy`` with a fixed label smoothing and, under ``batch_mix``, the current batch's
+    plan (set per batch by ``train_step``)."""
+
+    def __init__(self, label_smoothing: float):
+        self.label_smoothing, self.plan = float(label_smoothing), None
+
+    def __call__(self, logits, y):
+        return soft_cross_entropy(logits, y, self.plan, self.label_smoothing)
+
+
 def _fused_loss(loss_fn):
-    """Use the fused kernel for a default nn.CrossEntropyLoss (same math and reduction)."""
+    """Use the fused kernels for a default nn.CrossEntropyLoss (same math and reduction): the
+    hard-label kernel, or with ``label_smoothing > 0`` the soft-target one."""
     if isinstance(loss_fn, nn.CrossEntropyLoss) and loss_fn.weight is None and loss_fn.reduction == "mean" \
-            and loss_fn.label_smoothing == 0.0 and loss_fn.ignore_index == -100:
-        return cross_entropy
+            and loss_fn.ignore_index == -100:
+        if loss_fn.label_smoothing == 0.0:
+            return cross_entropy
+        if loss_fn.label_smoothing > 0.0:
+            return _SoftLoss(loss_fn.label_smoothing)
     return loss_fn
+
+
+def _mix_target(model):
+    """(whether the model's ``forward`` takes ``mix``, its image size or None): a plan is drawn for the
+    image the model sees, which for a uint8 device-input batch is not the batch's own size."""
+    import inspect
+
+    inner = getattr(model, "module", model)  # DistributedDataParallel forwards keyword arguments
+    takes = "mix" in inspect.signature(inner.forward).parameters
+    S = getattr(inner, "config", {}).get("image_size") if takes else None
+    return takes, (int(S) if S else None)
 
 
 def _accumulate(sums: torch.Tensor, loss: torch.Tensor, logits: torch.Tensor, y: torch.Tensor, lf) -> None:
     """sums += [batch loss, batch accuracy] on the device. With the fused cross-entropy the kernel's
     per-row argmax == label flags are summed by one small HIP kernel; otherwise argmax / eq / sum."""
     with torch.no_grad():
-        corr = fused_vit.last_correct if lf is cross_entropy else None
+        corr = fused_vit.last_correct if lf is cross_entropy or isinstance(lf, _SoftLoss) else None
         if corr is not None and sums.is_cuda and corr.numel() == logits.shape[0]:
             from . import _ext
 
@@ -102,8 +128,14 @@ def _set_sampler_epoch(dataloader, epoch: Optional[int]) -> None:
 
 def train_step(model: torch.nn.Module, dataloader, loss_fn: torch.nn.Module, optimizer: torch.optim.Optimizer,
                lr_scheduler, device, *, max_grad_norm: Optional[float] = 1.0,
-               epoch: Optional[int] = None, step_logger=None) -> Tuple[float, float]:
+               epoch: Optional[int] = None, step_logger=None, batch_mix=None) -> Tuple[float, float]:
     """One training epoch (reference GM/engine.py:9-79). Returns (train_loss, train_acc).
+
+    ``batch_mix`` (optional :class:`~.data.batch_mix.BatchMix`): per batch a mixup / CutMix plan is drawn
+    on the host and passed to the model (``model(X, mix=plan)``; a model whose ``forward`` has no ``mix``
+    parameter gets ``mix_reference(X, plan)`` instead), and the loss is ``soft_cross_entropy`` with the
+    plan's label weights and ``batch_mix.label_smoothing`` in place of ``loss_fn``. The accuracy counts
+    ``argmax == y``, the samples' own labels.
 
     ``epoch`` (optional) seeds a ``DistributedSampler``'s shuffle for this epoch. ``step_logger``
     (optional :class:`~.utils.metrics.StepLogger`) gets one record per batch: step time, img/s, lr,
@@ -111,7 +143,8 @@ def train_step(model: torch.nn.Module, dataloader, loss_fn: torch.nn.Module, opt
     all-reduce times — without a host synchronisation per step."""
     _set_sampler_epoch(dataloader, epoch)
     model.train()
-    lf = _fused_loss(loss_fn)
+    lf = _fused_loss(loss_fn) if batch_mix is None else _SoftLoss(batch_mix.label_smoothing)
+    takes_mix, mix_size = _mix_target(model) if batch_mix is not None else (False, None)
     sums = torch.zeros(2, dtype=torch.float32, device=device)
     nb = 0
     for X, y in prefetch(dataloader, device):
@@ -119,7 +152,16 @@ def train_step(model: torch.nn.Module, dataloader, loss_fn: torch.nn.Module, opt
             step_logger.begin()
         X, y = X.to(device, non_blocking=True), y.to(device, non_blocking=True)
         with range_push("forward"):  # ROCTX ranges (PVR_ROCTX=1, rocprofv3 --marker-trace)
-            y_pred = model(X)
+            if batch_mix is None:
+                y_pred = model(X)
+            else:
+                lf.plan = batch_mix.sample(X.shape[0], mix_size or X.shape[-2], mix_size or X.shape[-1])
+                if takes_mix:
+                    y_pred = model(X, mix=lf.plan)
+                else:
+                    from .data.batch_mix import mix_reference
+
+                    y_pred = model(mix_reference(X, lf.plan))
             loss = lf(y_pred, y)
         optimizer.zero_grad()
         with range_push("backward"):
@@ -158,11 +200,14 @@ def train(model: torch.nn.Module, train_dataloader, test_dataloader, optimizer: 
           loss_fn: torch.nn.Module, lr_scheduler, epochs: int, device, *, max_grad_norm: Optional[float] = 1.0,
           checkpoint_dir: Optional[str] = None, metrics_path: Optional[str] = None, start_epoch: int = 0,
           results: Optional[Dict[str, List]] = None, step_metrics_path: Optional[str] = None,
-          log_every: int = 50) -> Dict[str, List]:
+          log_every: int = 50, batch_mix=None) -> Dict[str, List]:
     """Train and test for ``epochs`` epochs (reference GM/engine.py:132-211).
 
     ``metrics_path``: one JSONL record per epoch. ``step_metrics_path``: one JSONL record per training
     step (:class:`~.utils.metrics.StepLogger`, flushed every ``log_every`` steps; rank 0 writes).
+
+    ``batch_mix``: mixup / CutMix / label smoothing of the training batches (see :func:`train_step`);
+    evaluation never mixes and keeps ``loss_fn``.
 
     Resume (new, optional): ``start_epoch`` epochs are already done (``load_checkpoint(...)["epoch"]``)
     and ``results`` holds their metrics; only epochs ``start_epoch + 1 .. epochs`` run, numbered as
@@ -183,7 +228,8 @@ def train(model: torch.nn.Module, train_dataloader, test_dataloader, optimizer: 
     for epoch in it:
         train_loss, train_acc = train_step(model=model, dataloader=train_dataloader, loss_fn=loss_fn,
                                            optimizer=optimizer, lr_scheduler=lr_scheduler, device=device,
-                                           max_grad_norm=max_grad_norm, epoch=epoch, step_logger=step_logger)
+                                           max_grad_norm=max_grad_norm, epoch=epoch, step_logger=step_logger,
+                                           batch_mix=batch_mix)
         if step_logger is not None:
             step_logger.flush()
         test_loss, test_acc = test_step(model=model, dataloader=test_dataloader, loss_fn=loss_fn, device=device)

@@ -202,11 +202,14 @@ class ViT(nn.Module):
         x = self.transformer_encoder(x)
         return self.layer_norm(x)
 
-    def forward(self, x: torch.Tensor, geom: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, geom: Optional[torch.Tensor] = None, mix=None) -> torch.Tensor:
+        """``mix`` (optional :class:`~..data.batch_mix.MixPlan`, training or eval): mixup / CutMix of the
+        batch as the model sees it, inside the patch-embedding kernels on the fused path and as
+        ``data.batch_mix.mix_reference`` after the preprocessing elsewhere. ``None``: no mixing."""
         x, pre = self._device_input(x, geom)
         if _ext.use_fused(x) and self._fused_supported(x, pre):
-            return self._forward_fused(x, pre)
-        x = self._preprocess_reference(x, pre)
+            return self._forward_fused(x, pre, mix)
+        x = self._mix_reference(self._preprocess_reference(x, pre), mix)
         x = self.forward_features(x)
         return self.classifier(x[:, 0])
 
@@ -268,6 +271,14 @@ class ViT(nn.Module):
         S = self.config["image_size"]
         return preprocess_reference(x, pre[0], pre[1], pre[2], (S, S))
 
+    @staticmethod
+    def _mix_reference(x: torch.Tensor, mix) -> torch.Tensor:
+        if mix is None:
+            return x
+        from ..data.batch_mix import mix_reference
+
+        return mix_reference(x, mix)
+
     # ------------------------------------------------------------------ fused path
     def _fused_supported(self, x: torch.Tensor, pre=None) -> bool:
         c = self.config
@@ -303,21 +314,22 @@ class ViT(nn.Module):
         _ext.ext().rng_next(rng, seed)  # seed = rng; rng += 1 (one device kernel, graph-replay safe)
         return seed
 
-    def _forward_fused(self, x: torch.Tensor, pre=None) -> torch.Tensor:
+    def _forward_fused(self, x: torch.Tensor, pre=None, mix=None) -> torch.Tensor:
         from ..ops.fused_vit import HeadFn
 
         # the head reads token 0 only: the last block may return the class-token rows alone ([B, D])
-        tokens, store, B, N = self._fused_encoder(x, pre, cls_rows=True)
+        tokens, store, B, N = self._fused_encoder(x, pre, cls_rows=True, mix=mix)
         head = self.classifier[0]
         return HeadFn.apply(tokens, B, N if tokens.shape[0] == B * N else 1, self.layer_norm.eps, store, self.layer_norm.weight, self.layer_norm.bias,
                             head.weight, head.bias)
 
-    def _fused_encoder(self, x: torch.Tensor, pre=None, cls_rows: bool = False):
+    def _fused_encoder(self, x: torch.Tensor, pre=None, cls_rows: bool = False, mix=None):
         """Patch embedding + every encoder block on the fused path: (bf16 tokens [B*N, D], store, B, N).
         Shared by this model's head and the classifier-free backbone (models/vit_no_classifier.py).
         ``cls_rows`` (a caller that reads token 0 of each image only): the last block may run on the
         class-token rows alone (ops/fused_vit.py ``CLS_LAST_BLOCK``), and ``tokens`` is then ``[B, D]``.
-        ``pre`` = ``(mean, std, geom)`` of a uint8 batch (:meth:`_device_input`), None for a float one."""
+        ``pre`` = ``(mean, std, geom)`` of a uint8 batch (:meth:`_device_input`), None for a float one.
+        ``mix``: the batch's ``MixPlan`` (None: none), applied by the patchify kernel."""
         from ..ops.fused_vit import (ATTN_SITE, EncoderBlockClsFn, EncoderBlockFn, PatchEmbedFn, PatchEmbedU8Fn, block_links,
                                      cls_last_block_ok, site_drop)
         from ..runtime.param_store import get_store
@@ -345,12 +357,12 @@ class ViT(nn.Module):
         conv = pe.patch_and_flatten[0]
         if pre is None:
             tokens = PatchEmbedFn.apply(x, c["patch_size"], store, seed, pe.dropout.p, training,
-                                        conv.weight, conv.bias, pe.class_token, pe.position_embedding)
+                                        conv.weight, conv.bias, pe.class_token, pe.position_embedding, mix)
         else:
             mean, std, geom = pre
             tokens = PatchEmbedU8Fn.apply(x, geom, mean, std, (c["image_size"], c["image_size"]), c["patch_size"], store, seed,
                                           pe.dropout.p, training, conv.weight, conv.bias, pe.class_token,
-                                          pe.position_embedding)
+                                          pe.position_embedding, mix)
         B = x.shape[0]
         N = pe.number_of_patches + 1
         f8 = self._fp8_state(dev, B * N)

@@ -89,20 +89,31 @@ def _patch_embed_bwd(ctx, dtokens) -> None:
     store.grad_ready([conv_w, conv_b, cls, pos])
 
 
+def _mix_args(mix, B, size, device):
+    """The patchify kernels' ``mix`` / ``mix_host`` arguments for a ``data.batch_mix.MixPlan`` (None: none):
+    the device table and the host copy the binding validates."""
+    if mix is None:
+        return {}
+    mix.check(B, size)
+    return dict(mix=mix.on(device)[0], mix_host=mix.rows)
+
+
 class PatchEmbedFn(torch.autograd.Function):
+    """``mix`` (optional ``MixPlan``): mixup / CutMix inside the gather, here and in PatchEmbedU8Fn."""
+
     @staticmethod
-    def forward(ctx, img, patch, store, seed, p_drop, training, conv_w, conv_b, cls, pos):
+    def forward(ctx, img, patch, store, seed, p_drop, training, conv_w, conv_b, cls, pos, mix=None):
         img = img.float().contiguous()
         B, C, H, W = img.shape
         n_p, kc, kp = _patch_geometry(C, H, W, patch)
         patches = torch.empty(B * n_p, kp, dtype=torch.bfloat16, device=img.device)
-        _ext.ext().im2col(img, patches, patch, kp)
+        _ext.ext().im2col(img, patches, patch, kp, **_mix_args(mix, B, (H, W), img.device))
         return _patch_embed_fwd(ctx, patches, B, n_p, kc, kp, store, seed, p_drop, training, conv_w, conv_b, cls, pos)
 
     @staticmethod
     def backward(ctx, dtokens):
         _patch_embed_bwd(ctx, dtokens)
-        return (None,) * 10
+        return (None,) * 11
 
 
 class PatchEmbedU8Fn(torch.autograd.Function):
@@ -112,18 +123,18 @@ class PatchEmbedU8Fn(torch.autograd.Function):
     while it writes the patch rows (data/device_input.py). ``geom`` None needs Hs x Ws == H x W."""
 
     @staticmethod
-    def forward(ctx, img, geom, mean, std, size, patch, store, seed, p_drop, training, conv_w, conv_b, cls, pos):
+    def forward(ctx, img, geom, mean, std, size, patch, store, seed, p_drop, training, conv_w, conv_b, cls, pos, mix=None):
         B, C = img.shape[0], img.shape[1]
         H, W = size
         n_p, kc, kp = _patch_geometry(C, H, W, patch)
         patches = torch.empty(B * n_p, kp, dtype=torch.bfloat16, device=img.device)
-        _ext.ext().im2col_u8(img, patches, list(mean), list(std), geom, H, W, patch, kp)
+        _ext.ext().im2col_u8(img, patches, list(mean), list(std), geom, H, W, patch, kp, **_mix_args(mix, B, (H, W), img.device))
         return _patch_embed_fwd(ctx, patches, B, n_p, kc, kp, store, seed, p_drop, training, conv_w, conv_b, cls, pos)
 
     @staticmethod
     def backward(ctx, dtokens):
         _patch_embed_bwd(ctx, dtokens)
-        return (None,) * 14
+        return (None,) * 15
 
 
 # test hook: bf16 outputs left unwritten on the fp8 path (only their fp8 copies are consumed) are
@@ -661,6 +672,77 @@ def cross_entropy(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         return loss
     last_correct = None
     return F.cross_entropy(logits, target)
+
+
+class SoftCrossEntropyFn(torch.autograd.Function):
+    """CrossEntropyFn for soft target rows ``(1 - eps) * (lam * onehot(ya) + (1 - lam) * onehot(yb)) + eps / C``
+    (csrc/xent.hip ``xent_soft_kernel``); ``correct`` flags ``argmax == ya``."""
+
+    @staticmethod
+    def forward(ctx, logits, ya, yb, lam, eps, correct):
+        ext = _ext.ext()
+        lf = logits.float().contiguous()
+        B = lf.shape[0]
+        dl = torch.empty_like(lf) if logits.requires_grad else None
+        mean = torch.empty((), dtype=torch.float32, device=lf.device)
+        ext.xent_soft(lf, ya, yb, lam, eps, dl, correct, 1.0 / B, mean.view(1))
+        ctx.save_for_backward(dl) if dl is not None else None
+        ctx.in_dtype = logits.dtype
+        return mean
+
+    @staticmethod
+    def backward(ctx, g):
+        (dl,) = ctx.saved_tensors
+        return (_ext.ext().scale_by(dl, g.float().reshape(1).contiguous()).to(ctx.in_dtype),) + (None,) * 5
+
+
+def soft_targets(target: torch.Tensor, num_classes: int, plan=None, label_smoothing: float = 0.0,
+                 dtype=torch.float32) -> torch.Tensor:
+    """The explicit target rows ``[B, C]`` of :func:`soft_cross_entropy` as torch ops."""
+    ya = target.long()
+    one_a = F.one_hot(ya, num_classes).to(dtype)
+    if plan is None:
+        q = one_a
+    else:
+        _, partner, lam = plan.on(target.device)
+        lam = lam.to(dtype).view(-1, 1)
+        q = lam * one_a + (1.0 - lam) * F.one_hot(ya.index_select(0, partner), num_classes).to(dtype)
+    return (1.0 - label_smoothing) * q + label_smoothing / num_classes
+
+
+_ONES: dict = {}
+
+
+def soft_cross_entropy(logits: torch.Tensor, target: torch.Tensor, plan=None, label_smoothing: float = 0.0) -> torch.Tensor:
+    """Mean cross-entropy against mixed and / or smoothed labels: sample ``b``'s target row is
+    ``(1 - eps) * (lam_b * onehot(y_b) + (1 - lam_b) * onehot(y_partner[b])) + eps / C`` with ``lam`` =
+    ``plan.lam_eff`` of a ``data.batch_mix.MixPlan`` (``plan=None``: no mixing) and ``eps`` = ``label_smoothing``.
+    On the GPU one fused kernel (loss, gradient, and the ``last_correct`` flags ``argmax == y_b``); on the
+    CPU ``F.cross_entropy`` on the explicit rows (torch's own ``label_smoothing`` when there is no plan)."""
+    global last_correct
+    eps = float(label_smoothing)
+    if plan is not None and plan.batch != logits.shape[0]:
+        raise ValueError(f"soft_cross_entropy: a plan for {plan.batch} samples with {logits.shape[0]} logit rows")
+    if _ext.use_fused(logits) and logits.dim() == 2 and target.dim() == 1:
+        B, dev = logits.shape[0], logits.device
+        ya = target.long().contiguous()
+        if plan is None:
+            yb = ya
+            lam = _ONES.get((dev, B))
+            if lam is None:
+                with torch.inference_mode(False):  # kept across calls: not an inference tensor
+                    lam = _ONES[(dev, B)] = torch.ones(B, dtype=torch.float32, device=dev)
+        else:
+            _, partner, lam = plan.on(dev)
+            yb = ya.index_select(0, partner)
+        correct = torch.empty(B, dtype=torch.int32, device=dev)
+        loss = SoftCrossEntropyFn.apply(logits, ya, yb, lam, eps, correct)
+        last_correct = correct
+        return loss
+    last_correct = None
+    if plan is None:
+        return F.cross_entropy(logits, target, label_smoothing=eps)
+    return F.cross_entropy(logits, soft_targets(target, logits.shape[1], plan, eps, logits.dtype))
 
 
 _UNIT: dict = {}
