@@ -67,6 +67,11 @@ def build_parser():
     p.add_argument("--mix-prob", type=float, default=1.0, help="probability that a batch is mixed")
     p.add_argument("--mix-switch-prob", type=float, default=0.5, help="with both: probability of CutMix over mixup")
     p.add_argument("--label-smoothing", type=float, default=0.0, metavar="E", help="label smoothing of the loss (0: off)")
+    p.add_argument("--model-ema", type=float, nargs="?", const=0.9999, default=None, metavar="DECAY",
+                   help="keep an exponential moving average of the weights (bare flag: 0.9999): it is what the test "
+                        "pass evaluates, checkpoints carry it and <name>_ema.pth is written beside the model")
+    p.add_argument("--model-ema-warmup", action="store_true",
+                   help="with --model-ema: ramp the decay, update n uses min(DECAY, (1 + n) / (10 + n))")
     return p
 
 
@@ -87,16 +92,19 @@ def main(argv=None) -> int:
     from ..data import DeviceInput, RandomResizedCropFlip, create_dataloaders, create_synthetic_dataloaders
     from ..data.transforms import default_vit_transform, uint8_transform
     from ..models import TinyVGG, vit
-    from ..optim import FusedAdam, param_groups_weight_decay, warmup_linear_decay
+    from ..optim import FusedAdam, ModelEma, param_groups_weight_decay, warmup_linear_decay
     from ..parallel import DistributedDataParallel, init_distributed, is_dist
     from .. import _ext
     from ..utils import load_checkpoint, save_model, set_seeds
+    from ..utils.checkpoint import save_ema
 
     args = build_parser().parse_args(argv)
     if args.dtype == "fp8" and args.model == "tinyvgg":
         raise SystemExit("--dtype fp8 applies to the ViT models")
     if args.device_preprocess and args.model == "tinyvgg":
         raise SystemExit("--device-preprocess applies to the ViT models")
+    if args.model_ema_warmup and args.model_ema is None:
+        raise SystemExit("--model-ema-warmup needs --model-ema")
     if not args.device_preprocess and (args.augment != "none" or args.source_size is not None):
         raise SystemExit("--augment and --source-size need --device-preprocess")
     src_size = args.source_size or args.image_size
@@ -131,11 +139,12 @@ def main(argv=None) -> int:
     else:
         opt = FusedAdam(groups, lr=args.lr, betas=(0.9, 0.999))
     sched = warmup_linear_decay(opt, args.epochs * len(train_dl), args.warmup_frac)
+    ema = ModelEma(model, decay=args.model_ema, warmup=args.model_ema_warmup) if args.model_ema is not None else None
     start_epoch, results = 0, None
     if args.resume:
         # --epochs is the TOTAL epoch count: a resumed run trains only the epochs not yet done, on the
         # same (restored) LR schedule, so it ends where the uninterrupted run would have
-        info = load_checkpoint(args.resume, model, opt, sched)
+        info = load_checkpoint(args.resume, model, opt, sched, model_ema=ema)
         start_epoch, results = int(info["epoch"]), info["results"]
         if _is_rank0():
             print(f"[INFO] Resumed {args.resume} at epoch {start_epoch} of {args.epochs}")
@@ -147,8 +156,12 @@ def main(argv=None) -> int:
                      loss_fn=torch.nn.CrossEntropyLoss(label_smoothing=args.label_smoothing), lr_scheduler=sched,
                      epochs=args.epochs, device=device, max_grad_norm=args.max_grad_norm, checkpoint_dir=args.checkpoint_dir,
                      metrics_path=args.metrics, start_epoch=start_epoch, results=results,
-                     batch_mix=build_batch_mix(args, rank))
-    save_model(model, args.save_dir, args.save_name or f"{args.model}_{args.epochs}_epochs.pth")
+                     batch_mix=build_batch_mix(args, rank), model_ema=ema)
+    name = args.save_name or f"{args.model}_{args.epochs}_epochs.pth"
+    save_model(model, args.save_dir, name)
+    if ema is not None:
+        stem, dot, suffix = name.rpartition(".")
+        save_ema(ema, args.save_dir, f"{stem}_ema{dot}{suffix}")
     return 0
 
 

@@ -612,15 +612,42 @@ GroupTable group_table(const torch::Tensor& groups, const char* who) {
   return t;
 }
 
+// Model EMA of an Adam pass (kernels.h AdamEma). ema: fp32, contiguous, on p's device, p's numel.
+// pair float32 [2] {decay, one_minus_decay}: a CUDA tensor is read by the kernel (graph-captured
+// steps), a CPU tensor travels in the kernel arguments. No ema: no EMA (the default kernels).
+pvr::AdamEma ema_args(const torch::Tensor& p, c10::optional<torch::Tensor>& ema, const c10::optional<torch::Tensor>& pair, const char* who) {
+  pvr::AdamEma a;
+  if (!ema.has_value() || !ema->defined()) return a;
+  TORCH_CHECK(ema->is_cuda() && ema->device() == p.device() && ema->scalar_type() == torch::kFloat32 && ema->is_contiguous() &&
+                  ema->numel() == p.numel(),
+              who, ": ema must be contiguous float32 on the parameters' device with their numel");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(ema->data_ptr()) % 16 == 0, who, ": ema must be 16-byte aligned");
+  TORCH_CHECK(pair.has_value() && pair->defined() && pair->scalar_type() == torch::kFloat32 && pair->numel() == 2 && pair->is_contiguous(),
+              who, ": ema needs ema_pair, float32 [2] {decay, 1 - decay}");
+  a.buf = ema->data_ptr<float>();
+  if (pair->is_cuda()) {
+    TORCH_CHECK(pair->device() == p.device(), who, ": ema_pair on another device");
+    a.pair = pair->data_ptr<float>();
+  } else {
+    a.decay = pair->data_ptr<float>()[0];
+    a.one_minus_decay = pair->data_ptr<float>()[1];
+  }
+  return a;
+}
+
 void adam(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, c10::optional<torch::Tensor> shadow, torch::Tensor seg_start,
-          torch::Tensor seg_group, torch::Tensor groups, c10::optional<torch::Tensor> clip, bool skip_nonfinite) {
+          torch::Tensor seg_group, torch::Tensor groups, c10::optional<torch::Tensor> clip, bool skip_nonfinite,
+          c10::optional<torch::Tensor> ema, c10::optional<torch::Tensor> ema_pair) {
   TORCH_CHECK(p.numel() == g.numel() && p.numel() == m.numel() && p.numel() == v.numel(), "adam: size mismatch");
   const GroupTable gt = group_table(groups, "adam");
   TORCH_CHECK(seg_start.scalar_type() == torch::kInt64 && seg_group.scalar_type() == torch::kInt32, "adam: segment table dtypes");
   uint16_t* sh = nullptr;
   if (shadow.has_value() && shadow->defined()) sh = const_cast<uint16_t*>(bf(*shadow, "shadow"));
+  if (ema.has_value() && ema->defined()) TORCH_CHECK(p.is_contiguous(), "adam: contiguous parameters");
+  const pvr::AdamEma ea = ema_args(p, ema, ema_pair, "adam");
   check(pvr_adam(f32_mut(p, "p"), f32(g, "g"), f32_mut(m, "m"), f32_mut(v, "v"), sh, p.numel(), seg_start.data_ptr<int64_t>(),
-                 seg_group.data_ptr<int>(), (int)seg_start.numel(), gt.dev, gt.host, gt.n, opt_ptr<const float>(clip), skip_nonfinite ? 1 : 0, stream()),
+                 seg_group.data_ptr<int>(), (int)seg_start.numel(), gt.dev, gt.host, gt.n, opt_ptr<const float>(clip), skip_nonfinite ? 1 : 0, ea,
+                 stream()),
         "adam");
 }
 
@@ -629,7 +656,8 @@ void adam(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, c1
 // fmeta int64 [nflat][4] {flat start, elements % 4 == 0, group, first float4} for everything else.
 void adam_t(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, torch::Tensor shadow, torch::Tensor shadow_t,
             torch::Tensor tmeta, int64_t ntiles, torch::Tensor fmeta, int64_t flat4, torch::Tensor groups,
-            c10::optional<torch::Tensor> clip, bool skip_nonfinite) {
+            c10::optional<torch::Tensor> clip, bool skip_nonfinite, c10::optional<torch::Tensor> ema,
+            c10::optional<torch::Tensor> ema_pair) {
   TORCH_CHECK(p.numel() == g.numel() && p.numel() == m.numel() && p.numel() == v.numel() && shadow.numel() == p.numel(),
               "adam_t: size mismatch");
   const GroupTable gt = group_table(groups, "adam_t");
@@ -640,10 +668,10 @@ void adam_t(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, 
   TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && m.is_contiguous() && v.is_contiguous() && shadow.is_contiguous() &&
                   shadow_t.is_contiguous(),
               "adam_t: contiguous buffers");
+  const pvr::AdamEma ea = ema_args(p, ema, ema_pair, "adam_t");
   check(pvr_adam_t(f32_mut(p, "p"), f32(g, "g"), f32_mut(m, "m"), f32_mut(v, "v"), bf_mut(shadow, "shadow"), bf_mut(shadow_t, "shadow_t"),
                    tmeta.data_ptr<int64_t>(), (int)tmeta.size(0), (int)ntiles, fmeta.data_ptr<int64_t>(), (int)fmeta.size(0), flat4,
-                   gt.dev, gt.host, gt.n, opt_ptr<const float>(clip), skip_nonfinite ? 1 : 0,
-                   stream()),
+                   gt.dev, gt.host, gt.n, opt_ptr<const float>(clip), skip_nonfinite ? 1 : 0, ea, stream()),
         "adam_t");
 }
 
@@ -1184,8 +1212,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dlogits"), py::arg("correct"), py::arg("grad_scale"), py::arg("mean") = py::none());
   m.def("grad_norm", &grad_norm);
   m.def("norm_partial_blocks", []() { return pvr_norm_partial_blocks(); });
-  m.def("adam", &adam);
-  m.def("adam_t", &adam_t);
+  m.def("adam", &adam, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("shadow"), py::arg("seg_start"),
+        py::arg("seg_group"), py::arg("groups"), py::arg("clip"), py::arg("skip_nonfinite"), py::arg("ema") = py::none(),
+        py::arg("ema_pair") = py::none());
+  m.def("adam_t", &adam_t, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("shadow"), py::arg("shadow_t"),
+        py::arg("tmeta"), py::arg("ntiles"), py::arg("fmeta"), py::arg("flat4"), py::arg("groups"), py::arg("clip"),
+        py::arg("skip_nonfinite"), py::arg("ema") = py::none(), py::arg("ema_pair") = py::none());
   m.def("scale_by_clip", &scale_by_clip);
   m.def("head_fwd", &head_fwd);
   m.def("head_bwd", &head_bwd, py::arg("dlogits"), py::arg("xhat"), py::arg("rstd"), py::arg("gamma"), py::arg("beta"), py::arg("W"),

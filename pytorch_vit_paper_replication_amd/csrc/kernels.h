@@ -20,6 +20,14 @@ struct AdamGroup {
 };
 static_assert(sizeof(AdamGroup) == 8 * sizeof(float), "AdamGroup is one float32 [8] row of the group table");
 
+// Model EMA updated inside the Adam pass: buf (fp32, the layout of p) becomes
+// decay * buf + one_minus_decay * p_new for every element the pass updates. pair: device
+// {decay, one_minus_decay} (graph-captured steps, whose kernel arguments are frozen), or null: the
+// by-value pair. buf null: no EMA.
+struct AdamEma {
+  float* buf = nullptr; const float* pair = nullptr; float decay = 0.f, one_minus_decay = 1.f;
+};
+
 // A dropout site: the element's 16-bit hash of (*seed + offset) is kept iff >= thr = round(p * 65536);
 // kept values scale by 65536 / (65536 - thr). seed null: no dropout.
 struct DropSite {
@@ -185,13 +193,14 @@ hipError_t pvr_grad_norm(const float* g, int64_t n, float max_norm, float* works
 // groups: device table, or null with host_groups [ngroups <= 8] copied into the kernel arguments
 hipError_t pvr_adam(float* p, const float* g, float* m, float* v, uint16_t* shadow, int64_t n, const int64_t* seg_start,
                     const int* seg_group, int nseg, const pvr::AdamGroup* groups, const pvr::AdamGroup* host_groups, int ngroups,
-                    const float* clip, int skip_nonfinite, hipStream_t s);
+                    const float* clip, int skip_nonfinite, pvr::AdamEma ema, hipStream_t s);
 hipError_t pvr_scale_by_clip(float* g, int64_t n, const float* clip, hipStream_t s);
 // Adam with the transposed bf16 shadow (adam_t_kernel): tmeta int64 [nmat][6], fmeta int64 [nflat][4]
 // (see the kernel), flat4 = float4s covered by fmeta.
 hipError_t pvr_adam_t(float* p, const float* g, float* m, float* v, uint16_t* shadow, uint16_t* shadow_t, const int64_t* tmeta,
                       int nmat, int ntiles, const int64_t* fmeta, int nflat, int64_t flat4, const pvr::AdamGroup* groups,
-                      const pvr::AdamGroup* host_groups, int ngroups, const float* clip, int skip_nonfinite, hipStream_t s);
+                      const pvr::AdamGroup* host_groups, int ngroups, const float* clip, int skip_nonfinite, pvr::AdamEma ema,
+                      hipStream_t s);
 
 // ---- fp8.hip
 hipError_t pvr_fp8_quant(const uint16_t* x, int64_t ldx, uint8_t* y, int64_t ldy, int64_t rows, int cols, const float* qscale,

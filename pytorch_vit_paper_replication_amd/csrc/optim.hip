@@ -18,9 +18,38 @@ struct AdamGroupArgs {
   AdamGroup g[MAX_ARG_GROUPS];
 };
 
+// Model EMA inside the Adam pass (AdamEma: kernels.h). The kernels are templates on EMA: the default
+// instantiation takes an empty argument and is the instruction stream it was without the feature; the
+// EMA one reads and writes one more fp32 buffer with the layout of p,
+//   ema = decay * ema + one_minus_decay * p_new
+// for exactly the elements Adam updates (frozen segments and a skipped non-finite step leave it alone).
+// Two products, not ema + w * (p - ema): decay 0 gives p_new and decay 1 leaves ema, bit for bit,
+// contracted to an fma or not.
+template <bool EMA> struct EmaArg {};
+template <> struct EmaArg<true> { AdamEma a; };
+
 namespace {
 
 constexpr int NORM_BLOCKS = 1024;
+
+// {decay, one_minus_decay} of this launch: the device pair (graph-captured steps) or the by-value one
+__device__ __forceinline__ float2 ema_pair(const AdamEma& a) {
+  return a.pair ? make_float2(a.pair[0], a.pair[1]) : make_float2(a.decay, a.one_minus_decay);
+}
+
+// Every call sits behind a test of the buffer pointer (which the host never leaves null), after the
+// Adam update of the values it reads: a branch of its own keeps the EMA's arithmetic out of the basic
+// block of the Adam update. In one block the vectoriser pairs operations across the two and changes
+// which of Adam's a * b + c are contracted, so the EMA instantiation rounded p, m and v differently from
+// the default one (tests/test_gpu_model_ema.py compares the two bit for bit). The branch is uniform.
+__device__ __forceinline__ void ema4(float* __restrict__ ema, int64_t e, const float4& pp, float2 dw) {
+  float4 ee = *(float4*)(ema + e);
+  ee.x = dw.x * ee.x + dw.y * pp.x;
+  ee.y = dw.x * ee.y + dw.y * pp.y;
+  ee.z = dw.x * ee.z + dw.y * pp.z;
+  ee.w = dw.x * ee.w + dw.y * pp.w;
+  *(float4*)(ema + e) = ee;
+}
 
 __global__ void __launch_bounds__(256) sumsq_partial_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ partial) {
   __shared__ float red[4];
@@ -61,13 +90,16 @@ __global__ void __launch_bounds__(256) norm_finalize_kernel(const float* __restr
 }
 
 // seg_start[i] = first flat index of segment i (sorted), seg_group[i] = its param group.
+template <bool EMA>
 __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, uint16_t* __restrict__ shadow, int64_t n,
                                                     const int64_t* __restrict__ seg_start, const int* __restrict__ seg_group, int nseg,
                                                     const AdamGroup* __restrict__ groups, AdamGroupArgs garg,
-                                                    const float* __restrict__ clip, int skip_nonfinite) {
+                                                    const float* __restrict__ clip, int skip_nonfinite, EmaArg<EMA> ea) {
   const float gscale = clip ? clip[1] : 1.f;
   if (clip && skip_nonfinite && clip[2] != 0.f) return;
+  float2 dw = make_float2(0.f, 0.f);
+  if constexpr (EMA) dw = ema_pair(ea.a);
   const int64_t n4 = n / 4;
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
     const int64_t e = i * 4;
@@ -102,6 +134,9 @@ __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const 
     ((float4*)p)[i] = pp;
     ((float4*)m)[i] = mm;
     ((float4*)v)[i] = vv;
+    if constexpr (EMA) {
+      if (ea.a.buf != nullptr) ema4(ea.a.buf, e, pp, dw);
+    }
     if (shadow) {
       uint2 o;
       o.x = pack2bf(pp.x, pp.y);
@@ -137,14 +172,17 @@ __device__ __forceinline__ void adam4(float4& pp, const float4& gg4, float4& mm,
   }
 }
 
+template <bool EMA>
 __global__ void __launch_bounds__(256) adam_t_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                       float* __restrict__ v, uint16_t* __restrict__ shadow, uint16_t* __restrict__ shadow_t,
                                                       const int64_t* __restrict__ tmeta, int nmat, int ntiles,
                                                       const int64_t* __restrict__ fmeta, int nflat, int64_t flat4,
                                                       const AdamGroup* __restrict__ groups, AdamGroupArgs garg,
-                                                      const float* __restrict__ clip, int skip_nonfinite) {
+                                                      const float* __restrict__ clip, int skip_nonfinite, EmaArg<EMA> ea) {
   const float gscale = clip ? clip[1] : 1.f;
   if (clip && skip_nonfinite && clip[2] != 0.f) return;
+  float2 dw = make_float2(0.f, 0.f);
+  if constexpr (EMA) dw = ema_pair(ea.a);
   const int tid = threadIdx.x;
   if ((int)blockIdx.x < ntiles) {
     __shared__ uint32_t tile[64][33];
@@ -163,6 +201,7 @@ __global__ void __launch_bounds__(256) adam_t_kernel(float* __restrict__ p, cons
     if (gi < 0) return;  // frozen: master, shadow and W^T unchanged
     const AdamGroup G = groups ? groups[gi] : garg.g[gi];
     const int cq = (tid & 15) * 4;
+    float4 pn[EMA ? 4 : 1];  // EMA: the four new values, averaged after the unrolled Adam updates
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       const int row = (tid >> 4) + 16 * it;
@@ -175,10 +214,18 @@ __global__ void __launch_bounds__(256) adam_t_kernel(float* __restrict__ p, cons
       *(float4*)(p + e) = pp;
       *(float4*)(m + e) = mm;
       *(float4*)(v + e) = vv;
+      if constexpr (EMA) pn[it] = pp;
       const uint32_t lo2 = pack2bf(pp.x, pp.y), hi2 = pack2bf(pp.z, pp.w);
       *(uint2*)(shadow + e) = make_uint2(lo2, hi2);
       tile[row][cq >> 1] = lo2;
       tile[row][(cq >> 1) + 1] = hi2;
+    }
+    if constexpr (EMA) {
+      if (ea.a.buf != nullptr) {
+#pragma unroll
+        for (int it = 0; it < 4; ++it)
+          ema4(ea.a.buf, soff + (int64_t)(r0 + (tid >> 4) + 16 * it) * C + c0 + cq, pn[it], dw);
+      }
     }
     __syncthreads();
 #pragma unroll
@@ -214,6 +261,9 @@ __global__ void __launch_bounds__(256) adam_t_kernel(float* __restrict__ p, cons
     *(float4*)(m + e) = mm;
     *(float4*)(v + e) = vv;
     *(uint2*)(shadow + e) = make_uint2(pack2bf(pp.x, pp.y), pack2bf(pp.z, pp.w));
+    if constexpr (EMA) {
+      if (ea.a.buf != nullptr) ema4(ea.a.buf, e, pp, dw);
+    }
   }
 }
 
@@ -244,7 +294,7 @@ extern "C" hipError_t pvr_grad_norm(const float* g, int64_t n, float max_norm, f
 extern "C" hipError_t pvr_adam(float* p, const float* g, float* m, float* v, uint16_t* shadow, int64_t n,
                                const int64_t* seg_start, const int* seg_group, int nseg, const pvr::AdamGroup* groups,
                                const pvr::AdamGroup* host_groups, int ngroups, const float* clip, int skip_nonfinite,
-                               hipStream_t s) {
+                               pvr::AdamEma ema, hipStream_t s) {
   using namespace pvr;
   if (n <= 0) return hipSuccess;
   if (n % 4 != 0) return hipErrorInvalidValue;
@@ -252,8 +302,13 @@ extern "C" hipError_t pvr_adam(float* p, const float* g, float* m, float* v, uin
   if (!groups && !adam_group_args(host_groups, ngroups, ga)) return hipErrorInvalidValue;
   int64_t blocks = (n / 4 + 255) / 256;
   if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p, g, m, v, shadow, n, seg_start, seg_group, nseg,
-                     groups, ga, clip, skip_nonfinite);
+  if (ema.buf) {
+    hipLaunchKernelGGL(adam_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, p, g, m, v, shadow, n, seg_start, seg_group,
+                       nseg, groups, ga, clip, skip_nonfinite, EmaArg<true>{ema});
+  } else {
+    hipLaunchKernelGGL(adam_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, p, g, m, v, shadow, n, seg_start, seg_group,
+                       nseg, groups, ga, clip, skip_nonfinite, EmaArg<false>{});
+  }
   return hipGetLastError();
 }
 
@@ -269,7 +324,7 @@ extern "C" hipError_t pvr_scale_by_clip(float* g, int64_t n, const float* clip, 
 extern "C" hipError_t pvr_adam_t(float* p, const float* g, float* m, float* v, uint16_t* shadow, uint16_t* shadow_t,
                                  const int64_t* tmeta, int nmat, int ntiles, const int64_t* fmeta, int nflat, int64_t flat4,
                                  const pvr::AdamGroup* groups, const pvr::AdamGroup* host_groups, int ngroups,
-                                 const float* clip, int skip_nonfinite, hipStream_t s) {
+                                 const float* clip, int skip_nonfinite, pvr::AdamEma ema, hipStream_t s) {
   using namespace pvr;
   if (nmat <= 0 || ntiles <= 0 || nflat <= 0) return hipErrorInvalidValue;
   AdamGroupArgs ga{};
@@ -277,7 +332,12 @@ extern "C" hipError_t pvr_adam_t(float* p, const float* g, float* m, float* v, u
   int64_t fb = (flat4 + 255) / 256;
   if (fb > 1024) fb = 1024;
   if (fb < 1) fb = 1;
-  hipLaunchKernelGGL(adam_t_kernel, dim3((unsigned)(ntiles + fb)), dim3(256), 0, s, p, g, m, v, shadow, shadow_t, tmeta, nmat,
-                     ntiles, fmeta, nflat, flat4, groups, ga, clip, skip_nonfinite);
+  if (ema.buf) {
+    hipLaunchKernelGGL(adam_t_kernel<true>, dim3((unsigned)(ntiles + fb)), dim3(256), 0, s, p, g, m, v, shadow, shadow_t, tmeta,
+                       nmat, ntiles, fmeta, nflat, flat4, groups, ga, clip, skip_nonfinite, EmaArg<true>{ema});
+  } else {
+    hipLaunchKernelGGL(adam_t_kernel<false>, dim3((unsigned)(ntiles + fb)), dim3(256), 0, s, p, g, m, v, shadow, shadow_t, tmeta,
+                       nmat, ntiles, fmeta, nflat, flat4, groups, ga, clip, skip_nonfinite, EmaArg<false>{});
+  }
   return hipGetLastError();
 }

@@ -20,6 +20,7 @@ MI355X-oriented differences (no behaviour change):
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -128,7 +129,7 @@ def _set_sampler_epoch(dataloader, epoch: Optional[int]) -> None:
 
 def train_step(model: torch.nn.Module, dataloader, loss_fn: torch.nn.Module, optimizer: torch.optim.Optimizer,
                lr_scheduler, device, *, max_grad_norm: Optional[float] = 1.0,
-               epoch: Optional[int] = None, step_logger=None, batch_mix=None) -> Tuple[float, float]:
+               epoch: Optional[int] = None, step_logger=None, batch_mix=None, model_ema=None) -> Tuple[float, float]:
     """One training epoch (reference GM/engine.py:9-79). Returns (train_loss, train_acc).
 
     ``batch_mix`` (optional :class:`~.data.batch_mix.BatchMix`): per batch a mixup / CutMix plan is drawn
@@ -136,6 +137,10 @@ def train_step(model: torch.nn.Module, dataloader, loss_fn: torch.nn.Module, opt
     parameter gets ``mix_reference(X, plan)`` instead), and the loss is ``soft_cross_entropy`` with the
     plan's label weights and ``batch_mix.label_smoothing`` in place of ``loss_fn``. The accuracy counts
     ``argmax == y``, the samples' own labels.
+
+    ``model_ema`` (optional :class:`~.optim.ModelEma`): attached to the optimizer on first use; a
+    ``FusedAdam`` then updates the average inside its step, for any other optimizer it is updated here
+    after the step.
 
     ``epoch`` (optional) seeds a ``DistributedSampler``'s shuffle for this epoch. ``step_logger``
     (optional :class:`~.utils.metrics.StepLogger`) gets one record per batch: step time, img/s, lr,
@@ -147,6 +152,8 @@ def train_step(model: torch.nn.Module, dataloader, loss_fn: torch.nn.Module, opt
     takes_mix, mix_size = _mix_target(model) if batch_mix is not None else (False, None)
     sums = torch.zeros(2, dtype=torch.float32, device=device)
     nb = 0
+    if model_ema is not None and not model_ema.updated_by(optimizer):
+        model_ema.attach(optimizer)
     for X, y in prefetch(dataloader, device):
         if step_logger is not None:
             step_logger.begin()
@@ -168,6 +175,8 @@ def train_step(model: torch.nn.Module, dataloader, loss_fn: torch.nn.Module, opt
             fused_vit.backward(loss)
         with range_push("optimizer"):
             norm = _clip_and_step(model, optimizer, max_grad_norm)
+            if model_ema is not None and not model_ema.updated_by(optimizer):
+                model_ema.update()
         lr = optimizer.param_groups[0]["lr"]
         lr_scheduler.step()
         _accumulate(sums, loss, y_pred, y, lf)
@@ -200,7 +209,7 @@ def train(model: torch.nn.Module, train_dataloader, test_dataloader, optimizer: 
           loss_fn: torch.nn.Module, lr_scheduler, epochs: int, device, *, max_grad_norm: Optional[float] = 1.0,
           checkpoint_dir: Optional[str] = None, metrics_path: Optional[str] = None, start_epoch: int = 0,
           results: Optional[Dict[str, List]] = None, step_metrics_path: Optional[str] = None,
-          log_every: int = 50, batch_mix=None) -> Dict[str, List]:
+          log_every: int = 50, batch_mix=None, model_ema=None) -> Dict[str, List]:
     """Train and test for ``epochs`` epochs (reference GM/engine.py:132-211).
 
     ``metrics_path``: one JSONL record per epoch. ``step_metrics_path``: one JSONL record per training
@@ -208,6 +217,10 @@ def train(model: torch.nn.Module, train_dataloader, test_dataloader, optimizer: 
 
     ``batch_mix``: mixup / CutMix / label smoothing of the training batches (see :func:`train_step`);
     evaluation never mixes and keeps ``loss_fn``.
+
+    ``model_ema`` (optional :class:`~.optim.ModelEma`): averaged during training (see :func:`train_step`);
+    the test pass runs inside ``model_ema.applied()``, so ``test_loss`` / ``test_acc`` are those of the
+    averaged weights, and checkpoints carry the average.
 
     Resume (new, optional): ``start_epoch`` epochs are already done (``load_checkpoint(...)["epoch"]``)
     and ``results`` holds their metrics; only epochs ``start_epoch + 1 .. epochs`` run, numbered as
@@ -229,10 +242,11 @@ def train(model: torch.nn.Module, train_dataloader, test_dataloader, optimizer: 
         train_loss, train_acc = train_step(model=model, dataloader=train_dataloader, loss_fn=loss_fn,
                                            optimizer=optimizer, lr_scheduler=lr_scheduler, device=device,
                                            max_grad_norm=max_grad_norm, epoch=epoch, step_logger=step_logger,
-                                           batch_mix=batch_mix)
+                                           batch_mix=batch_mix, model_ema=model_ema)
         if step_logger is not None:
             step_logger.flush()
-        test_loss, test_acc = test_step(model=model, dataloader=test_dataloader, loss_fn=loss_fn, device=device)
+        with model_ema.applied() if model_ema is not None else contextlib.nullcontext():
+            test_loss, test_acc = test_step(model=model, dataloader=test_dataloader, loss_fn=loss_fn, device=device)
         if _rank0():
             print(f"Epoch: {epoch + 1} | "
                   f"train_loss: {train_loss:.4f} | "
@@ -252,5 +266,5 @@ def train(model: torch.nn.Module, train_dataloader, test_dataloader, optimizer: 
             from .utils.checkpoint import save_checkpoint
 
             save_checkpoint(checkpoint_dir, model=model, optimizer=optimizer, lr_scheduler=lr_scheduler,
-                            epoch=epoch + 1, results=results)
+                            epoch=epoch + 1, results=results, model_ema=model_ema)
     return results

@@ -8,7 +8,8 @@ On the fused GPU path all parameters live in one ``ParamStore``; a step is
   Adam:                          one kernel: g*coef (+wd*p) -> m, v -> p -> bf16 shadow (and the
                                  transposed bf16 shadow W^T of the 2-D encoder weights)
 so clip_grad_norm_ + optimizer.step() (SURVEY.md K14+K15, ~1000 small launches) become 3 launches
-with no host synchronisation. Elsewhere (CPU, or parameters outside a store) it falls back to the
+with no host synchronisation. With a :class:`~.ema.ModelEma` attached the same kernel also updates the
+model EMA from the new parameter value it holds in registers (one more fp32 read and write per element). Elsewhere (CPU, or parameters outside a store) it falls back to the
 exact torch.optim.Adam single-tensor math.
 """
 from __future__ import annotations
@@ -56,6 +57,10 @@ class FusedAdam(torch.optim.Optimizer):
         self._table_dev: Optional[torch.Tensor] = None
         self._table_ring = []  # pinned host buffers + events (host may run a few steps ahead)
         self._ring_i = 0
+        # model EMA updated inside the Adam pass (ModelEma.attach); in hipGraph mode its per-step
+        # {decay, 1 - decay} pair rides behind the group table in the same upload
+        self._ema = None
+        self._ema_pair_dev: Optional[torch.Tensor] = None
 
     # ------------------------------------------------------------------ helpers
     def _all_params(self):
@@ -171,15 +176,21 @@ class FusedAdam(torch.optim.Optimizer):
 
     def _alloc_table(self, device, ring: int = 4) -> None:
         G = len(self.param_groups)
-        self._table_dev = torch.zeros(G, 8, dtype=torch.float32, device=device)
-        self._table_ring = [(torch.zeros(G, 8, dtype=torch.float32).pin_memory(), torch.cuda.Event()) for _ in range(ring)]
+        # [G][8] group table, then the 2-float EMA pair (32-byte aligned behind it): one buffer, one copy
+        self._upload_dev = torch.zeros(G * 8 + 2, dtype=torch.float32, device=device)
+        self._table_dev = self._upload_dev[:G * 8].view(G, 8)
+        self._ema_pair_dev = self._upload_dev[G * 8:]
+        self._table_ring = [(torch.zeros(G * 8 + 2, dtype=torch.float32).pin_memory(), torch.cuda.Event()) for _ in range(ring)]
 
-    def _upload_table(self, step: int) -> None:
+    def _upload_table(self, step: int, ema_pair=None) -> None:
         host, ev = self._table_ring[self._ring_i % len(self._table_ring)]
         self._ring_i += 1
         ev.synchronize()  # the copy that last used this pinned buffer has executed
-        self._group_array(max(step, 1), host.numpy())
-        self._table_dev.copy_(host, non_blocking=True)
+        arr = host.numpy()
+        self._group_array(max(step, 1), arr[:-2].reshape(-1, 8))
+        if ema_pair is not None:
+            arr[-2:] = ema_pair
+        self._upload_dev.copy_(host, non_blocking=True)
         ev.record()
 
     # ------------------------------------------------------------------ hipGraph support
@@ -196,10 +207,14 @@ class FusedAdam(torch.optim.Optimizer):
             self.graph_prepare(advance=False)
 
     def graph_prepare(self, advance: bool = True) -> None:
-        """Advance the step counter and upload this step's lr / bias corrections (stream-ordered)."""
+        """Advance the step counter and upload this step's lr / bias corrections (stream-ordered); with a
+        model EMA attached, its decay pair for this step too (advancing the EMA's update counter)."""
         if advance:
             self.step_count += 1
-        self._upload_table(self.step_count)
+        pair = None
+        if self._ema is not None:
+            pair = self._ema.next_pair() if advance else self._ema.pair_at(self._ema.num_updates)
+        self._upload_table(self.step_count, pair)
 
     # ------------------------------------------------------------------ public
     def zero_grad(self, set_to_none: bool = True):
@@ -250,18 +265,27 @@ class FusedAdam(torch.optim.Optimizer):
                 _ext.ext().grad_norm(store.grad_flat, 0.0, ws, clip)  # max_norm 0 -> coef 1, flag only
                 use_clip = True
             table = self._group_table(step, store.device)
+            ema = self._ema
+            ema_buf = ema.fused_buffer(store) if ema is not None else None
+            ema_kw = {}
+            if ema_buf is not None:
+                # captured steps read the pair graph_prepare() uploaded; eager ones take it by value
+                pair = self._ema_pair_dev if self._graph else torch.from_numpy(np.array(ema.next_pair(), dtype=np.float32))
+                ema_kw = dict(ema=ema_buf, ema_pair=pair)
             tt = self._transposed_tables(store)  # Adam also writes the bf16 W^T shadow when it can
             if tt is not None and tt[3] > 0:
                 # master, m, v, bf16 shadow and the dgrad GEMMs' W^T shadow in one pass
                 store.ensure_transposed()  # only if something else changed the weights since
                 _ext.ext().adam_t(store.flat, store.grad_flat, m, v, store.shadow, store.shadow_t, tt[0], tt[1], tt[2], tt[3],
-                                  table, clip if use_clip else None, self.skip_nonfinite)
+                                  table, clip if use_clip else None, self.skip_nonfinite, **ema_kw)
                 store.mark_shadow_fresh(transposed=True)
             else:
                 _ext.ext().adam(store.flat, store.grad_flat, m, v, store.shadow, seg_start, seg_group, table,
-                                clip if use_clip else None, self.skip_nonfinite)
+                                clip if use_clip else None, self.skip_nonfinite, **ema_kw)
                 store.mark_shadow_fresh()
             self._pending_clip = False
+            if ema is not None and ema_buf is None:
+                ema.update()  # the EMA's model is not this store's: torch ops
             return loss
         # ---------------- reference math (torch.optim.Adam, single-tensor, maximize=False)
         if clip_norm is not None:
@@ -291,6 +315,8 @@ class FusedAdam(torch.optim.Optimizer):
                 step_size = lr / bc1
                 denom = (st["exp_avg_sq"].sqrt() / math.sqrt(bc2)).add_(eps)
                 p.addcdiv_(st["exp_avg"], denom, value=-step_size)
+        if self._ema is not None:
+            self._ema.update()
         return loss
 
     def state_dict(self):

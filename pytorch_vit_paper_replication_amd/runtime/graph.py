@@ -8,8 +8,9 @@ later step is then one ``hipGraphLaunch``, replayed against static input buffers
 
 What makes the fused step capture-safe:
   * no host synchronisation anywhere in the step (device-side metrics, clip and non-finite checks);
-  * ``FusedAdam.graph_mode()``: lr / bias corrections come from a persistent device table that
-    ``graph_prepare()`` refreshes before each replay, so LR schedules keep working;
+  * ``FusedAdam.graph_mode()``: lr / bias corrections (and an attached ``ModelEma``'s decay pair) come
+    from a persistent device table that ``graph_prepare()`` refreshes before each replay, so LR
+    schedules and the EMA's warm-up keep working;
   * dropout seeds advance on the device (``ViT._dropout_seed`` increments a device counter);
   * the weight-gradient side stream forks / joins with events, which capture as graph edges;
   * every scratch tensor is allocated from the graph's private memory pool during capture.

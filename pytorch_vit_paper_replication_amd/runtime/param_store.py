@@ -16,6 +16,7 @@ bucketer) as soon as a group of parameters has its final gradient.
 """
 from __future__ import annotations
 
+import contextlib
 import weakref
 from typing import Any, Callable, Dict, Iterable, List, Optional, Tuple
 
@@ -206,6 +207,35 @@ class ParamStore:
                 for p in self._t_params:
                     self._t_views[id(p)].copy_(self.bf16(p).t())
         self._t_dirty = False
+
+    # ------------------------------------------------------------------ another set of weights
+    @contextlib.contextmanager
+    def swapped(self, flat_other: torch.Tensor):
+        """Compute with another set of weights (a model EMA): inside the context ``flat`` holds the
+        values of ``flat_other`` (fp32, this store's layout) and ``flat_other`` the trained weights;
+        the bf16 shadow and the W^T shadow follow. The *contents* are exchanged, not the buffers: every
+        ``p.data``, bf16 view and W^T view points into the existing buffers, and kernels read biases,
+        LayerNorm weights, the class token and the position embedding from the fp32 master. On exit
+        everything is exchanged back, bit for bit. Not under a stream capture."""
+        if flat_other.shape != self.flat.shape or flat_other.dtype != self.flat.dtype or flat_other.device != self.flat.device:
+            raise ValueError("swapped: expected a float32 buffer with the store's layout on its device")
+        if self.flat.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("ParamStore.swapped() cannot run under a stream capture")
+        self._exchange(flat_other)
+        try:
+            yield self
+        finally:
+            self._exchange(flat_other)
+
+    def _exchange(self, flat_other: torch.Tensor) -> None:
+        self.join_side()  # weight gradients may be in flight (they read the bf16 shadows)
+        with torch.inference_mode(False), torch.no_grad():
+            tmp = self.flat.clone()
+            self.flat.copy_(flat_other)
+            flat_other.copy_(tmp)
+        self.refresh_shadow(force=True)
+        if self._t_params:
+            self.ensure_transposed()
 
     def layout_key(self):
         """Identity of the bf16 shadow buffers (changes when register_transposed reallocates)."""

@@ -7,8 +7,8 @@ here as fp32 CPU tensors with their own storages, so the file loads into the ref
 are views into the fused path's flat store.
 
 New: ``load_model`` and full training-state ``save_checkpoint``/``load_checkpoint`` (model,
-optimizer, scheduler, epoch, RNG, results, and the fused path's runtime state: the device dropout
-counter and the fp8 delayed-scaling histories) for a bit-exact resume — the reference had no load
+optimizer, scheduler, epoch, RNG, results, the model EMA, and the fused path's runtime state: the device
+dropout counter and the fp8 delayed-scaling histories) for a bit-exact resume — the reference had no load
 path at all (GM/utils.py:7-35 only saves).
 Only rank 0 writes under torch.distributed.
 """
@@ -45,13 +45,25 @@ def save_model(model: torch.nn.Module, target_dir: str, model_name: str):
     return model_save_path
 
 
+def save_ema(model_ema, target_dir: str, model_name: str):
+    """``save_model`` for a :class:`~..optim.ModelEma`: the averaged weights under the model's keys."""
+    target_dir_path = Path(target_dir)
+    target_dir_path.mkdir(parents=True, exist_ok=True)
+    assert model_name.endswith(".pth") or model_name.endswith(".pt"), "model_name should end with '.pt' or '.pth'"
+    path = target_dir_path / model_name
+    if _rank0():
+        print(f"[INFO] Saving model EMA to: {path}")
+        torch.save(obj=model_ema.state_dict(), f=path)
+    return path
+
+
 def load_model(model: torch.nn.Module, path: str, strict: bool = True, map_location="cpu"):
     sd = torch.load(path, map_location=map_location, weights_only=True)
     return _unwrap(model).load_state_dict(sd, strict=strict)
 
 
 def save_checkpoint(target_dir: str, model: torch.nn.Module, optimizer=None, lr_scheduler=None, epoch: int = 0,
-                    results: Optional[Dict[str, Any]] = None, name: str = "checkpoint.pt") -> Optional[Path]:
+                    results: Optional[Dict[str, Any]] = None, name: str = "checkpoint.pt", model_ema=None) -> Optional[Path]:
     if not _rank0():
         return None
     d = Path(target_dir)
@@ -78,6 +90,10 @@ def save_checkpoint(target_dir: str, model: torch.nn.Module, optimizer=None, lr_
         # fused-path state outside state_dict(): the device dropout counter and the fp8 scaling
         # histories; without them a resumed run draws other dropout masks / re-calibrates fp8
         state["runtime"] = rt()
+    if model_ema is not None:
+        # tensors and numbers only: load_checkpoint reads with weights_only=True
+        state["model_ema"] = {"params": model_ema.state_dict(), "num_updates": int(model_ema.num_updates),
+                              "decay": float(model_ema.decay), "warmup": bool(model_ema.warmup)}
     tmp = d / (name + ".tmp")
     torch.save(state, tmp)
     os.replace(tmp, d / name)
@@ -85,12 +101,16 @@ def save_checkpoint(target_dir: str, model: torch.nn.Module, optimizer=None, lr_
 
 
 def load_checkpoint(path: str, model: torch.nn.Module, optimizer=None, lr_scheduler=None, map_location="cpu",
-                    restore_rng: bool = True) -> Dict[str, Any]:
+                    restore_rng: bool = True, model_ema=None) -> Dict[str, Any]:
     """Restores state saved by ``save_checkpoint``; returns ``{"epoch", "results"}``.
 
     The file is read with ``weights_only=True``: everything ``save_checkpoint`` writes (tensors,
     dicts/lists of numbers, the optimizer and LR-scheduler state dicts, RNG byte tensors) loads
-    without unpickling arbitrary objects, so a ``--resume`` path cannot execute code."""
+    without unpickling arbitrary objects, so a ``--resume`` path cannot execute code.
+
+    ``model_ema`` (optional :class:`~..optim.ModelEma`): its averaged weights and update counter are
+    restored (its own ``decay`` / ``warmup`` stay as constructed). A checkpoint written without an EMA
+    starts the average from the loaded model's weights."""
     state = torch.load(path, map_location=map_location, weights_only=True)
     _unwrap(model).load_state_dict(state["model"])
     if optimizer is not None and "optimizer" in state:
@@ -99,6 +119,18 @@ def load_checkpoint(path: str, model: torch.nn.Module, optimizer=None, lr_schedu
         lr_scheduler.load_state_dict(state["lr_scheduler"])
     if "runtime" in state and hasattr(_unwrap(model), "load_runtime_state_dict"):
         _unwrap(model).load_runtime_state_dict(state["runtime"])
+    if model_ema is not None:
+        saved = state.get("model_ema")
+        if saved is not None:
+            model_ema.load_state_dict(saved["params"])
+            model_ema.num_updates = int(saved["num_updates"])
+            if _rank0() and (float(saved["decay"]) != model_ema.decay or bool(saved["warmup"]) != model_ema.warmup):
+                print(f"[INFO] Model EMA continues with decay={model_ema.decay} warmup={model_ema.warmup} "
+                      f"(checkpoint: decay={float(saved['decay'])} warmup={bool(saved['warmup'])})")
+        else:
+            model_ema.reset()
+            if _rank0():
+                print(f"[INFO] {path} holds no model EMA: the average starts from the loaded weights")
     if restore_rng and "torch_rng" in state:
         torch.set_rng_state(state["torch_rng"])
         if torch.cuda.is_available() and "cuda_rng" in state:
