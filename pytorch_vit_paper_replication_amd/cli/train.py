@@ -52,6 +52,10 @@ def build_parser():
     p.add_argument("--fp8-bf16-wgrad", action="store_true", help="fp8: keep the weight-gradient GEMMs bf16")
     p.add_argument("--dropout", type=float, default=None,
                    help="override the MLP and embedding dropout of the ViT preset (0.1 = the reference's)")
+    p.add_argument("--drop-path", type=float, default=0.0, metavar="RATE",
+                   help="ViT: stochastic depth, the last block's drop rate (0: off; not with --dtype fp8)")
+    p.add_argument("--drop-path-schedule", choices=["linear", "constant"], default="linear",
+                   help="with --drop-path: rates rising linearly with depth from 0 to RATE, or RATE in every block")
     p.add_argument("--deterministic", action="store_true",
                    help="fixed-order reductions instead of float atomics: bitwise-repeatable gradients")
     p.add_argument("--bucket-mb", type=float, default=28.0, help="DDP gradient bucket size (MiB)")
@@ -103,6 +107,10 @@ def main(argv=None) -> int:
         raise SystemExit("--dtype fp8 applies to the ViT models")
     if args.device_preprocess and args.model == "tinyvgg":
         raise SystemExit("--device-preprocess applies to the ViT models")
+    if args.drop_path and args.model == "tinyvgg":
+        raise SystemExit("--drop-path applies to the ViT models")
+    if args.drop_path and args.dtype == "fp8":
+        raise SystemExit("--drop-path does not combine with --dtype fp8")
     if args.model_ema_warmup and args.model_ema is None:
         raise SystemExit("--model-ema-warmup needs --model-ema")
     if not args.device_preprocess and (args.augment != "none" or args.source_size is not None):
@@ -124,7 +132,8 @@ def main(argv=None) -> int:
         model = TinyVGG(input_shape=3, hidden_units=args.hidden_units, output_shape=ncls)
     else:
         drop = {} if args.dropout is None else dict(mlp_dropout=args.dropout, embedding_dropout=args.dropout)
-        model = vit(args.model, image_size=args.image_size, num_classes=ncls, **drop)
+        model = vit(args.model, image_size=args.image_size, num_classes=ncls, drop_path=args.drop_path,
+                    drop_path_schedule=args.drop_path_schedule, **drop)
         if args.dtype == "fp8":  # before a resume: the checkpoint's fp8 scaling state needs it
             model.enable_fp8(wgrad=not args.fp8_bf16_wgrad, grad_fmt=args.fp8_grad)
         if args.device_preprocess:
@@ -148,6 +157,12 @@ def main(argv=None) -> int:
         start_epoch, results = int(info["epoch"]), info["results"]
         if _is_rank0():
             print(f"[INFO] Resumed {args.resume} at epoch {start_epoch} of {args.epochs}")
+            saved = info.get("config") or {}
+            was = (saved.get("drop_path", 0.0), saved.get("drop_path_schedule", "linear"))
+            cfg = getattr(model, "config", None) or {}
+            now = (cfg.get("drop_path", 0.0), cfg.get("drop_path_schedule", "linear"))
+            if was != now and (was[0] or now[0]):
+                print(f"[INFO] The run continues with --drop-path {now[0]} ({now[1]}); the checkpoint was written with {was[0]} ({was[1]})")
     net = (DistributedDataParallel(model, bucket_cap_mb=args.bucket_mb,
                                    comm_dtype=torch.bfloat16 if args.comm_dtype == "bf16" else None)
            if is_dist() else model)

@@ -87,6 +87,14 @@ pvr::DropSite drop_args(const c10::optional<torch::Tensor>& seed, int64_t seed_o
   }
   return d;
 }
+// A drop-path site (per-sample DropSite, csrc/kernels.h): the same thr / scale rule as drop_args.
+// dp_p == 0: none (seed unread).
+pvr::DropSite drop_path_args(const c10::optional<torch::Tensor>& seed, int64_t seed_offset, double dp_p, int64_t dp_rows,
+                             const char* what) {
+  TORCH_CHECK(dp_p >= 0.0 && dp_p <= 1.0, what, ": drop_path rate must be in [0, 1]");
+  if (dp_p > 0.0) TORCH_CHECK(dp_rows >= 1 && dp_rows < (int64_t(1) << 31), what, ": drop_path needs rows per sample >= 1");
+  return drop_args(seed, seed_offset, dp_p, what);
+}
 // GemmParams keeps the site flat (the GEMM kernels take the struct by value); untouched without dropout
 void set_drop(pvr::GemmParams& p, const pvr::DropSite& d) {
   if (!d.seed) return;
@@ -188,7 +196,7 @@ void gemm(torch::Tensor A, bool a_kcontig, torch::Tensor B, bool b_kcontig, torc
           int64_t row_offset, c10::optional<torch::Tensor> seed, int64_t seed_offset, double drop_p, int64_t k_split,
           int64_t tile_cfg, c10::optional<torch::Tensor> dbg, c10::optional<torch::Tensor> colsum,
           int64_t epi_staged, int64_t tail_limit, c10::optional<torch::Tensor> reduce_out, bool reduce_acc,
-          int64_t drop_row_mul) {
+          int64_t drop_row_mul, c10::optional<torch::Tensor> dp_seed, int64_t dp_offset, double dp_p, int64_t dp_rows) {
   pvr::GemmParams p{};
   TORCH_CHECK(drop_row_mul >= 0 && (drop_row_mul == 0 || (tile_cfg == 0 && row_group == 0)) && M * std::max<int64_t>(drop_row_mul, 1) < (int64_t(1) << 31),
               "gemm: drop_row_mul (mask of every drop_row_mul-th row of a larger tensor) needs tile 0 and no row remap");
@@ -232,6 +240,19 @@ void gemm(torch::Tensor A, bool a_kcontig, torch::Tensor B, bool b_kcontig, torc
   p.row_group = (int)row_group; p.row_stride_group = (int)row_stride_group; p.row_offset = (int)row_offset;
   set_drop(p, drop_args(seed, seed_offset, drop_p, "gemm"));
   p.k_split_len = k_split > 0 ? (int)(((k_split + 63) / 64) * 64) : (int)(((K + 63) / 64) * 64);
+  if (dp_p > 0.0) {
+    // drop path of the residual branch: the bf16 residual forward GEMMs on tiles 0, 6, 12, 13
+    const pvr::DropSite dp = drop_path_args(dp_seed, dp_offset, dp_p, dp_rows, "gemm: drop_path");
+    TORCH_CHECK(epi == 0 && p.resid != nullptr, "gemm: drop_path needs the residual epilogue (EPI_BF16 with resid)");
+    TORCH_CHECK(a_kcontig && b_kcontig && row_group == 0 && p.addend == nullptr && p.k_split_len >= K,
+                "gemm: drop_path does not combine with row_group / addend / split-K / transposed operands");
+    TORCH_CHECK(tile_cfg == 0 || tile_cfg == 6 || tile_cfg == 12 || tile_cfg == 13,
+                "gemm: drop_path runs on tiles 0, 6, 12 and 13 (not the wave-specialised tile 15 or the split-K tile 14)");
+    TORCH_CHECK(p.seed_ptr == nullptr || p.seed_ptr == dp.seed, "gemm: drop_path and dropout must share the seed tensor");
+    TORCH_CHECK(M / dp_rows + 1 < (int64_t(1) << 31), "gemm: drop_path sample index");
+    p.seed_ptr = dp.seed;
+    p.dp_thr = dp.thr; p.dp_scale = dp.scale; p.dp_seed_offset = dp.offset; p.dp_rows = (int)dp_rows;
+  }
   p.epi = (int)epi;
   p.tile_cfg = (int)tile_cfg;
   // tail_limit: -1 = no split tail, 0 = unlimited, n > 0 = at most n workgroups in the split round
@@ -303,7 +324,8 @@ void layernorm_bwd(torch::Tensor dy, int64_t dy_stride, torch::Tensor x, int64_t
                    c10::optional<torch::Tensor> dsum, c10::optional<torch::Tensor> dz, c10::optional<torch::Tensor> seed,
                    int64_t seed_offset, double drop_p, c10::optional<torch::Tensor> q_out,
                    c10::optional<torch::Tensor> q_scale, c10::optional<torch::Tensor> q_amax, bool dz_nostore,
-                   int64_t q_fmt, int64_t dres_every) {
+                   int64_t q_fmt, int64_t dres_every, c10::optional<torch::Tensor> dp_seed, int64_t dp_offset, double dp_p,
+                   int64_t dp_rows) {
   const int64_t D = w.numel();
   pvr::LnBwdParams p{};
   TORCH_CHECK(dres_every >= 0, "layernorm_bwd: dres_every >= 0");
@@ -321,11 +343,17 @@ void layernorm_bwd(torch::Tensor dy, int64_t dy_stride, torch::Tensor x, int64_t
   p.dw = opt_ptr<float>(dw); p.db = opt_ptr<float>(db); p.dsum = opt_ptr<float>(dsum);
   const bool has_dz = dz.has_value() && dz->defined();
   if (has_dz) {
-    TORCH_CHECK(drop_p > 0.0, "layernorm_bwd: dz is the dropout backward, it needs drop_p > 0");
+    TORCH_CHECK(drop_p > 0.0 || dp_p > 0.0, "layernorm_bwd: dz is the dropout / drop_path backward, it needs drop_p > 0 or a drop_path rate > 0");
     p.dz = const_cast<uint16_t*>(bf(*dz, "dz"));
     p.dz_stride = ld_of(*dz, "dz");
   }
   p.drop = drop_args(seed, seed_offset, has_dz ? drop_p : 0.0, "layernorm_bwd");
+  if (dp_p > 0.0) {
+    TORCH_CHECK(has_dz, "layernorm_bwd: drop_path scales the dz output, it needs dz");
+    TORCH_CHECK(!(q_out.has_value() && q_out->defined()), "layernorm_bwd: drop_path does not combine with the fp8 copy (q_out)");
+    p.dpath = drop_path_args(dp_seed, dp_offset, dp_p, dp_rows, "layernorm_bwd: drop_path");
+    p.dp_rows = (int)dp_rows;
+  }
   p.dz_nostore = dz_nostore ? 1 : 0;
   // optional e5m2 copy of the last-written gradient (dz if given, else dx) with a delayed scale
   // and an amax record: the producer-side quantization for the next fp8 dgrad GEMM
@@ -400,9 +428,15 @@ void transpose_batched(torch::Tensor src, torch::Tensor dst, torch::Tensor meta,
 
 void colsum(torch::Tensor dy, int64_t rows, int64_t N, c10::optional<torch::Tensor> db, c10::optional<torch::Tensor> dz,
             c10::optional<torch::Tensor> seed, int64_t seed_offset, double drop_p, c10::optional<torch::Tensor> q_out,
-            c10::optional<torch::Tensor> q_scale, c10::optional<torch::Tensor> q_amax, int64_t q_fmt, int64_t row_mul) {
+            c10::optional<torch::Tensor> q_scale, c10::optional<torch::Tensor> q_amax, int64_t q_fmt, int64_t row_mul,
+            c10::optional<torch::Tensor> dp_seed, int64_t dp_offset, double dp_p, int64_t dp_rows) {
   TORCH_CHECK(row_mul >= 1 && rows * row_mul < (int64_t(1) << 31), "colsum: row_mul >= 1 and rows * row_mul < 2^31");
   const pvr::DropSite d = drop_args(seed, seed_offset, drop_p, "colsum");
+  pvr::DropSite dp;
+  if (dp_p > 0.0) {
+    TORCH_CHECK(!(q_out.has_value() && q_out->defined()), "colsum: drop_path does not combine with the fp8 copy (q_out)");
+    dp = drop_path_args(dp_seed, dp_offset, dp_p, dp_rows, "colsum: drop_path");
+  }
   int64_t ldz = 0;
   uint16_t* dzp = nullptr;
   if (dz.has_value() && dz->defined()) { dzp = const_cast<uint16_t*>(bf(*dz, "dz")); ldz = ld_of(*dz, "dz"); }
@@ -410,8 +444,19 @@ void colsum(torch::Tensor dy, int64_t rows, int64_t N, c10::optional<torch::Tens
   const pvr::Fp8Copy q = fp8_copy(q_out, q_scale, q_amax, q_fmt, rows, N, 8, "colsum");
   check(pvr_colsum(bf(dy, "dy"), ld_of(dy, "dy"), (int)rows, (int)N, opt_ptr<float>(db), dzp, ldz, d, q,
                    g_deterministic && opt_ptr<float>(db) ? det_scratch((int64_t)pvr_colsum_part_rows((int)rows) * N, dy.options()) : nullptr,
-                   (int)row_mul, stream()),
+                   (int)row_mul, dp, (int)std::max<int64_t>(dp_rows, 1), stream()),
         "colsum");
+}
+
+// s [B] float32: the drop-path scale vector of site (seed + site_offset) at rate p, 0 or 65536 / (65536 - thr)
+// per sample, exactly the draws the fused kernels make (the torch fallback's and the tests' replay)
+torch::Tensor drop_path_scale(torch::Tensor seed, int64_t site_offset, double p, int64_t B) {
+  TORCH_CHECK(B >= 0 && B < (int64_t(1) << 31), "drop_path_scale: B");
+  auto out = torch::ones({B}, seed.options().dtype(torch::kFloat32));
+  if (p <= 0.0 || B == 0) return out;
+  const pvr::DropSite dp = drop_path_args(seed, site_offset, p, 1, "drop_path_scale");
+  check(pvr_drop_path_scale(dp, out.data_ptr<float>(), (int)B, stream()), "drop_path_scale");
+  return out;
 }
 
 // A batch-mix plan for the patchify kernels (csrc/kernels.h MixRow): `mix` int32 [B, 8] on the image's
@@ -1178,7 +1223,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("row_offset"), py::arg("seed"), py::arg("seed_offset"), py::arg("drop_p"), py::arg("k_split"),
         py::arg("tile_cfg"), py::arg("dbg") = py::none(), py::arg("colsum") = py::none(),
         py::arg("epi_staged") = 0, py::arg("tail_limit") = 0, py::arg("reduce_out") = py::none(), py::arg("reduce_acc") = true,
-        py::arg("drop_row_mul") = 0);
+        py::arg("drop_row_mul") = 0, py::arg("dp_seed") = py::none(), py::arg("dp_offset") = 0, py::arg("dp_p") = 0.0,
+        py::arg("dp_rows") = 1);
+  m.def("drop_path_scale", &drop_path_scale, py::arg("seed"), py::arg("site_offset"), py::arg("p"), py::arg("B"));
   m.def("splitk_timeouts", &splitk_timeouts, py::arg("like"), py::arg("reset") = false);
   m.def("num_cus", &num_cus);
   m.def("layernorm_fwd", &layernorm_fwd);
@@ -1189,7 +1236,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dx_stride"), py::arg("dw"), py::arg("db"), py::arg("rows"), py::arg("dsum") = py::none(),
         py::arg("dz") = py::none(), py::arg("seed") = py::none(), py::arg("seed_offset") = 0, py::arg("drop_p") = 0.0,
         py::arg("q_out") = py::none(), py::arg("q_scale") = py::none(), py::arg("q_amax") = py::none(),
-        py::arg("dz_nostore") = false, py::arg("q_fmt") = 1, py::arg("dres_every") = 0);
+        py::arg("dz_nostore") = false, py::arg("q_fmt") = 1, py::arg("dres_every") = 0, py::arg("dp_seed") = py::none(),
+        py::arg("dp_offset") = 0, py::arg("dp_p") = 0.0, py::arg("dp_rows") = 1);
   m.def("cast_f32_bf16", &cast_f32_bf16);
   m.def("splitk_epilogue", &splitk_epilogue);
   m.def("attn_bwd_bias_rows", &attn_bwd_bias_rows, py::arg("B"), py::arg("N"), py::arg("H"), py::arg("D"), py::arg("drop") = false);
@@ -1199,7 +1247,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("transpose_batched", &transpose_batched);
   m.def("colsum", &colsum, py::arg("dy"), py::arg("rows"), py::arg("N"), py::arg("db"), py::arg("dz"), py::arg("seed"),
         py::arg("seed_offset"), py::arg("drop_p"), py::arg("q_out") = py::none(), py::arg("q_scale") = py::none(),
-        py::arg("q_amax") = py::none(), py::arg("q_fmt") = 1, py::arg("row_mul") = 1);
+        py::arg("q_amax") = py::none(), py::arg("q_fmt") = 1, py::arg("row_mul") = 1, py::arg("dp_seed") = py::none(),
+        py::arg("dp_offset") = 0, py::arg("dp_p") = 0.0, py::arg("dp_rows") = 1);
   m.def("im2col", &im2col, py::arg("img"), py::arg("out"), py::arg("P"), py::arg("Kp"), py::arg("mix") = py::none(),
         py::arg("mix_host") = py::none());
   m.def("im2col_u8", &im2col_u8, py::arg("img"), py::arg("out"), py::arg("mean"), py::arg("std"), py::arg("geom"), py::arg("H"),

@@ -182,6 +182,11 @@ PVR_DEV uint32_t rng_hash(uint64_t seed, uint64_t idx) {
 PVR_DEV bool rng_keep(uint64_t seed, uint64_t idx, uint32_t thr16) {
   return ((rng_hash(seed, idx >> 1) >> ((idx & 1) * 16)) & 0xFFFFu) >= thr16;
 }
+// rng_keep for an index below 2^32 with the seed's key at hand (key = rng_key(seed)): the per-sample
+// draw of a drop-path site, one hash per row.
+PVR_DEV bool rng_keep_32(uint32_t key, uint32_t idx, uint32_t thr16) {
+  return ((rng_mix32((idx >> 1) ^ key) >> ((idx & 1) * 16)) & 0xFFFFu) >= thr16;
+}
 // Keep decisions of 4 consecutive elements from an even idx with idx + 3 < 2^32 (key = rng_key(seed)):
 // the same hashes as two rng_keep2 calls (high word 0), in 32-bit index arithmetic.
 PVR_DEV void rng_keep4_32(uint32_t key, uint32_t idx_even, uint32_t thr16, bool (&k)[4]) {

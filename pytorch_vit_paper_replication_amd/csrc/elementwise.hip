@@ -29,12 +29,16 @@ __global__ void __launch_bounds__(256) cast_f32_bf16_kernel(const float* __restr
 // r * row_mul of a larger [rows * row_mul][N] tensor (1: this one; > 1: its class-token rows, compact).
 // Q8: also the fp8 copy (qfmt 1 e5m2, 0 e4m3) of the (masked) gradient, q[r][n] = fp8(v * *qscale), and its amax record
 // (the fp8 dgrad operand of the same tensor whose column sums are the bias gradient: one read, two uses)
-template <bool Q8>
+// DP: the branch's drop-path row scale too, v = s[r / dp_rows] * mask * scale * dy (s = 0 or dp_scale per
+// sample; independent of row_mul); the element and row scales fold into one fp32 factor per row.
+template <bool Q8, bool DP = false>
 __global__ void __launch_bounds__(256) colsum_kernel(const uint16_t* __restrict__ dy, int64_t ld, int rows, int N,
                                                       float* __restrict__ db, uint16_t* __restrict__ dz, int64_t ld_dz,
                                                       const uint64_t* seed_ptr, uint64_t seed_off, uint32_t thr, float scale,
                                                       uint8_t* __restrict__ qout, int64_t ld_q, const float* __restrict__ qscale,
-                                                      unsigned* __restrict__ amax, int qfmt, float* __restrict__ part, int row_mul) {
+                                                      unsigned* __restrict__ amax, int qfmt, float* __restrict__ part, int row_mul,
+                                                      const uint64_t* dp_seed_ptr, uint64_t dp_off, uint32_t dp_thr, float dp_scale,
+                                                      int dp_rows) {
   __shared__ float red[4][64 * 8];
   const float qs = Q8 ? *qscale : 1.f;
   float qam = 0.f;
@@ -43,6 +47,12 @@ __global__ void __launch_bounds__(256) colsum_kernel(const uint16_t* __restrict_
   const bool act = c * 8 < N;
   const uint64_t seed = thr ? (*seed_ptr + seed_off) : 0ull;
   float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint32_t dkey = 0u;
+  float dfk = 0.f;
+  if constexpr (DP) {
+    dkey = rng_key(*dp_seed_ptr + dp_off);
+    dfk = (thr ? scale : 1.f) * dp_scale;
+  }
   if (act) {
     // 4 rows per trip with their loads issued together (clamped rows, so the loads are
     // unconditional and the compiler counts them instead of draining vmcnt per row)
@@ -63,7 +73,16 @@ __global__ void __launch_bounds__(256) colsum_kernel(const uint16_t* __restrict_
           v[2 * j] = bf2f(w[j] & 0xFFFF);
           v[2 * j + 1] = bf2f(w[j] >> 16);
         }
-        if (thr) {
+        if constexpr (DP) {
+          const float rf = rng_keep_32(dkey, (uint32_t)r / (uint32_t)dp_rows, dp_thr) ? dfk : 0.f;  // wave-uniform
+#pragma unroll
+          for (int j = 0; j < 8; j += 2) {
+            bool k0 = true, k1 = true;
+            if (thr) rng_keep2(seed, (uint64_t)r * row_mul * N + c * 8 + j, thr, k0, k1);
+            v[j] = k0 ? v[j] * rf : 0.f;
+            v[j + 1] = k1 ? v[j + 1] * rf : 0.f;
+          }
+        } else if (thr) {
 #pragma unroll
           for (int j = 0; j < 8; j += 2) {
             bool k0, k1;
@@ -77,6 +96,16 @@ __global__ void __launch_bounds__(256) colsum_kernel(const uint16_t* __restrict_
           o.x = pack2bf(v[0], v[1]); o.y = pack2bf(v[2], v[3]);
           o.z = pack2bf(v[4], v[5]); o.w = pack2bf(v[6], v[7]);
           *(uint4*)(dz + (int64_t)r * ld_dz + c * 8) = o;
+          if constexpr (DP) {
+            // as in ln_bwd_kernel's drop-path instantiations (layernorm.hip): the bias gradient of a
+            // drop-path branch sums the bf16 dz values that its weight-gradient GEMM reads
+            const uint32_t ow[4] = {o.x, o.y, o.z, o.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              v[2 * j] = bf2f(ow[j] & 0xFFFF);
+              v[2 * j + 1] = bf2f(ow[j] >> 16);
+            }
+          }
         }
         if constexpr (Q8) {
           float vm = 0.f;
@@ -110,6 +139,13 @@ __global__ void __launch_bounds__(256) colsum_kernel(const uint16_t* __restrict_
       if (!(m <= 0.f)) atomicMax(amax, __float_as_uint(m));
     }
   }
+}
+
+// s[b] = drop-path scale of sample b at a site: 0 (dropped) or scale (see DropSite in kernels.h)
+__global__ void __launch_bounds__(256) drop_path_scale_kernel(const uint64_t* seed_ptr, uint64_t off, uint32_t thr, float scale,
+                                                               float* __restrict__ out, int B) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b < B) out[b] = rng_keep(*seed_ptr + off, (uint64_t)b, thr) ? scale : 0.f;
 }
 
 // One mixed pixel of the patchify kernels' MIX variants (MixRow in kernels.h): fp32, contraction off
@@ -734,20 +770,33 @@ extern "C" int pvr_colsum_part_rows(int rows) {
 }
 
 extern "C" hipError_t pvr_colsum(const uint16_t* dy, int64_t ld, int rows, int N, float* db, uint16_t* dz, int64_t ld_dz,
-                                 pvr::DropSite drop, pvr::Fp8Copy q, float* part, int row_mul, hipStream_t s) {
+                                 pvr::DropSite drop, pvr::Fp8Copy q, float* part, int row_mul, pvr::DropSite dpath, int dp_rows,
+                                 hipStream_t s) {
   using namespace pvr;
   if (rows <= 0) return hipSuccess;
   if (row_mul < 1 || (int64_t)rows * row_mul >= (1ll << 31)) return hipErrorInvalidValue;
   if (N % 8 != 0 || (q.fmt != 0 && q.fmt != 1)) return hipErrorInvalidValue;
   if (q.out && (!q.scale || !q.amax || q.ld % 8 != 0 || reinterpret_cast<uintptr_t>(q.out) % 8 != 0)) return hipErrorInvalidValue;
+  const bool has_dp = dpath.seed && dpath.thr;
+  if (has_dp && (q.out || dp_rows < 1 || dpath.thr > 65535u)) return hipErrorInvalidValue;  // drop path: bf16 only
   const int gx = (N / 8 + 63) / 64;
   const int gy = pvr_colsum_part_rows(rows);
   if (!db) part = nullptr;
-  hipLaunchKernelGGL(q.out ? colsum_kernel<true> : colsum_kernel<false>, dim3(gx, gy), dim3(256), 0, s, dy, ld, rows, N, db, dz, ld_dz,
-                     drop.seed, drop.offset, drop.thr, drop.scale, q.out, q.ld, q.scale, q.amax, q.fmt, part, row_mul);
+  hipLaunchKernelGGL(q.out ? colsum_kernel<true> : has_dp ? (colsum_kernel<false, true>) : colsum_kernel<false>, dim3(gx, gy), dim3(256), 0,
+                     s, dy, ld, rows, N, db, dz, ld_dz, drop.seed, drop.offset, drop.thr, drop.scale, q.out, q.ld, q.scale, q.amax, q.fmt,
+                     part, row_mul, dpath.seed, dpath.offset, has_dp ? dpath.thr : 0u, dpath.scale, dp_rows);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || !part) return e;
   return pvr_rows_reduce(part, gy, N, N, db, nullptr, nullptr, s);
+}
+
+extern "C" hipError_t pvr_drop_path_scale(pvr::DropSite dpath, float* s_out, int B, hipStream_t s) {
+  using namespace pvr;
+  if (B <= 0) return hipSuccess;
+  if (!dpath.seed || !s_out || dpath.thr > 65535u) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(drop_path_scale_kernel, dim3((B + 255) / 256), dim3(256), 0, s, dpath.seed, dpath.offset, dpath.thr, dpath.scale,
+                     s_out, B);
+  return hipGetLastError();
 }
 
 extern "C" hipError_t pvr_im2col(const float* img, uint16_t* out, int B, int C, int H, int W, int P, int Kp,

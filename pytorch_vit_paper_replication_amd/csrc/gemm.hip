@@ -29,6 +29,42 @@ enum GemmEpi : int {
   EPI_DGELU = 2,       // out = acc * aux   (aux as saved by EPI_GELU)            (bf16)
   EPI_F32_ATOMIC = 3,  // out += acc                                             (f32 atomics)
   EPI_F32_STORE = 4,   // out = acc                                              (f32)
+  // EPI_BF16 with the drop-path row scale (GemmParams::dp_*). Internal: pvr_gemm selects it for
+  // epi == EPI_BF16 with dp_thr > 0, so the term is a template parameter of every kernel and the
+  // EPI_BF16 instantiations carry none of it.
+  EPI_BF16_DP = 5,
+};
+constexpr bool epi_bf16(int e) { return e == EPI_BF16 || e == EPI_BF16_DP; }
+
+// Drop-path state of one epilogue call (EPI_BF16_DP), wave-uniform. factor(row) is 0 for a row of a
+// dropped sample, else the fp32 product drop_scale * dp_scale that multiplies (acc + bias) once: the two
+// scalings of the definition folded into one factor per row, so a kept element is rounded once before
+// the residual add. One hash per row (sample indices are < 2^31: the hash's high word is a no-op). The
+// sample of a row needs no division where samples have >= 128 rows (token matrices): the epilogue's
+// rows lie in [row0, row0 + 256), at most two sample boundaries past row0's sample, which one scalar
+// division per call locates. Shorter samples (class-token rows, tiny images) divide per row.
+struct DpRowScale {
+  uint32_t key, b0, r0;
+  int row0;
+  float fkeep;
+  PVR_DEV void init(const GemmParams& p, int first_row) {
+    key = rng_key(*p.seed_ptr + p.dp_seed_offset);
+    fkeep = p.drop_scale * p.dp_scale;
+    row0 = __builtin_amdgcn_readfirstlane(first_row);
+    b0 = (uint32_t)row0 / (uint32_t)p.dp_rows;
+    r0 = (uint32_t)row0 - b0 * (uint32_t)p.dp_rows;
+  }
+  PVR_DEV float factor(const GemmParams& p, int row) const {
+    const uint32_t d = (uint32_t)p.dp_rows;
+    uint32_t b;
+    if (d >= 128u) {  // uniform
+      const uint32_t r = r0 + (uint32_t)(row - row0);  // < d + 256 <= 3 d
+      b = b0 + (r >= d ? 1u : 0u) + (r >= 2u * d ? 1u : 0u);
+    } else {
+      b = (uint32_t)row / d;
+    }
+    return rng_keep_32(key, b, p.dp_thr) ? fkeep : 0.f;
+  }
 };
 
 
@@ -146,7 +182,7 @@ PVR_DEV void load_row(const GemmParams& p, int m, int64_t orow, int nb, int g, R
   for (int j = 0; j < FN; ++j) {
     const int n = nb + 16 * j + 4 * g;
     if (n >= p.N) continue;
-    if constexpr (EPI == EPI_BF16) {
+    if constexpr (epi_bf16(EPI)) {
       if (p.resid) in.r[j] = *(const uint2*)(p.resid + (int64_t)m * p.ld_resid + n);
       if (p.addend) in.a[j] = *(const float4*)(p.addend + (orow % p.addend_period) * p.N + n);
     } else if constexpr (EPI == EPI_DGELU) {
@@ -166,11 +202,13 @@ PVR_DEV void epilogue(const GemmParams& p, v4f (&acc)[FM][FN], int mb, int nb, i
     // lane holds C[m = mb + 16i + li][n = nb + 16j + 4g + r], r = 0..3 (4 consecutive columns)
     const uint64_t seed = (p.drop_thr ? *p.seed_ptr : 0ull) + p.seed_offset;
     const float deq = p.scale_a ? (*p.scale_a) * (*p.scale_b) : 1.f;
+    DpRowScale dps{};
+    if constexpr (EPI == EPI_BF16_DP) dps.init(p, mb);
     float4 bias[FN];
 #pragma unroll
     for (int j = 0; j < FN; ++j) {
       bias[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if constexpr (EPI == EPI_BF16 || EPI == EPI_GELU) {
+      if constexpr (epi_bf16(EPI) || EPI == EPI_GELU) {
         const int n = nb + 16 * j + 4 * g;
         if (p.bias && n < p.N) bias[j] = *(const float4*)(p.bias + n);
       }
@@ -186,27 +224,35 @@ PVR_DEV void epilogue(const GemmParams& p, v4f (&acc)[FM][FN], int mb, int nb, i
       const int64_t orow = out_row(p, m);
       if (i + 1 < FM) load_row<FN, EPI>(p, m + 16, out_row(p, m + 16), nb, g, nxt);
       if (m < p.M) {
+        float rf = 1.f;  // drop path: this row's factor (0: its sample's branch is dropped)
+        if constexpr (EPI == EPI_BF16_DP) rf = dps.factor(p, m);
 #pragma unroll
         for (int j = 0; j < FN; ++j) {
           const int n = nb + 16 * j + 4 * g;
           if (n >= p.N) continue;
           float v[4] = {acc[i][j][0] * deq, acc[i][j][1] * deq, acc[i][j][2] * deq, acc[i][j][3] * deq};
           bool keep[4] = {true, true, true, true};
-          if constexpr (EPI == EPI_BF16 || EPI == EPI_GELU) {
+          if constexpr (epi_bf16(EPI) || EPI == EPI_GELU) {
             if (p.drop_thr) {
               const uint64_t idx = (uint64_t)(p.drop_row_mul ? (int64_t)m * p.drop_row_mul : orow) * p.N + n;
               rng_keep2(seed, idx, p.drop_thr, keep[0], keep[1]);
               rng_keep2(seed, idx + 2, p.drop_thr, keep[2], keep[3]);
             }
           }
-          if constexpr (EPI == EPI_BF16 || EPI == EPI_GELU) {
+          if constexpr (epi_bf16(EPI) || EPI == EPI_GELU) {
             v[0] += bias[j].x; v[1] += bias[j].y; v[2] += bias[j].z; v[3] += bias[j].w;
           }
-          if constexpr (EPI == EPI_BF16) {
+          if constexpr (epi_bf16(EPI)) {
             if (p.addend) {
               v[0] += cur.a[j].x; v[1] += cur.a[j].y; v[2] += cur.a[j].z; v[3] += cur.a[j].w;
             }
-            if (p.drop_thr) {
+            if constexpr (EPI == EPI_BF16_DP) {
+              // a dropped row adds -0 to its residual: the sum is the residual's own bits (+0 would turn a -0 into +0)
+              const bool rk = rf != 0.f;
+              const float zero = rk ? 0.f : -0.f;
+#pragma unroll
+              for (int r = 0; r < 4; ++r) v[r] = keep[r] && rk ? v[r] * rf : zero;
+            } else if (p.drop_thr) {
 #pragma unroll
               for (int r = 0; r < 4; ++r) v[r] = keep[r] ? v[r] * p.drop_scale : 0.f;
             }
@@ -998,7 +1044,7 @@ PVR_DEV void epilogue_direct(const GemmParams& p, v4f (&acc)[8][4], char* smem, 
       make_rsrc((const uint16_t*)p.C + (int64_t)mb * p.ldc, rows && !p.c_skip ? (uint32_t)(((int64_t)(rows - 1) * p.ldc + p.N) * 2) : 0);
   __amdgpu_buffer_rsrc_t xrs = crs;  // residual (BF16) / aux (GELU store, DGELU load)
   int64_t ldx = p.ldc;
-  if constexpr (EPI == EPI_BF16 && RES) {
+  if constexpr (epi_bf16(EPI) && RES) {
     xrs = make_rsrc(p.resid + (int64_t)mb * p.ld_resid, rows ? (uint32_t)(((int64_t)(rows - 1) * p.ld_resid + p.N) * 2) : 0);
     ldx = p.ld_resid;
   } else if constexpr (EPI == EPI_GELU || EPI == EPI_DGELU) {
@@ -1018,7 +1064,7 @@ PVR_DEV void epilogue_direct(const GemmParams& p, v4f (&acc)[8][4], char* smem, 
     vx[jp] = okc ? (uint32_t)((li * ldx + c0[jp]) * 2) : OOB;
 #pragma unroll
     for (int e = 0; e < 8; ++e) bias[jp][e] = 0.f;
-    if constexpr (EPI == EPI_BF16 || EPI == EPI_GELU) {
+    if constexpr (epi_bf16(EPI) || EPI == EPI_GELU) {
       const uint32_t vb = okc ? (uint32_t)(c0[jp] * 4) : OOB;
       const v4f b0 = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(brs, vb, 0, 0));
       const v4f b1 = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(brs, vb + 16, 0, 0));
@@ -1029,6 +1075,10 @@ PVR_DEV void epilogue_direct(const GemmParams& p, v4f (&acc)[8][4], char* smem, 
   const uint64_t seed = (p.drop_thr ? *p.seed_ptr : 0ull) + p.seed_offset;
   const uint32_t key = p.drop_thr ? rng_key(seed) : 0u;
   const bool idx32 = (uint64_t)p.M * (uint64_t)p.N + 8 <= 0xFFFFFFFFull;
+  // drop path (EPI_BF16_DP): the row factor is computed per fragment row inside the loop below (one
+  // VGPR live next to the accumulators) from wave-uniform state
+  DpRowScale dps{};
+  if constexpr (EPI == EPI_BF16_DP) dps.init(p, mb);
   float csum[2][8];
 #pragma unroll
   for (int jp = 0; jp < 2; ++jp)
@@ -1039,7 +1089,7 @@ PVR_DEV void epilogue_direct(const GemmParams& p, v4f (&acc)[8][4], char* smem, 
   // rows before it without holding all 64 VGPRs at once (which spilled to scratch next to the 128
   // accumulators). Row offsets go into the VGPR offset: the SGPR offset of a buffer access is outside
   // its range check, so rows past M would be accessed.
-  constexpr bool HAS_IN = (EPI == EPI_BF16 && RES) || EPI == EPI_DGELU;
+  constexpr bool HAS_IN = (epi_bf16(EPI) && RES) || EPI == EPI_DGELU;
   constexpr int RING = 4;
   // fp8 copy of the GELU / dGELU output (fp8 GEMMs only): 8 bytes per lane and fragment row
   constexpr bool QOK = SCALED && (EPI == EPI_GELU || EPI == EPI_DGELU);
@@ -1061,6 +1111,8 @@ PVR_DEV void epilogue_direct(const GemmParams& p, v4f (&acc)[8][4], char* smem, 
     if (i == 1) stamp(p, 4);  // diagnostic builds only (p.dbg): row 0 done (bias / first inputs landed)
     const uint32_t so_c = (uint32_t)(i * 16 * (int)p.ldc * 2), so_x = (uint32_t)(i * 16 * (int)ldx * 2);
     const int m = mb + 16 * i + li;
+    float rf = 1.f;
+    if constexpr (EPI == EPI_BF16_DP) rf = dps.factor(p, m);
 #pragma unroll
     for (int jp = 0; jp < 2; ++jp) {
       v4u xin = {0u, 0u, 0u, 0u};
@@ -1079,7 +1131,7 @@ PVR_DEV void epilogue_direct(const GemmParams& p, v4f (&acc)[8][4], char* smem, 
         v[4 + r] = SCALED ? b * deq : b;
       }
       bool keep[8] = {true, true, true, true, true, true, true, true};
-      if constexpr (EPI == EPI_BF16 || EPI == EPI_GELU) {
+      if constexpr (epi_bf16(EPI) || EPI == EPI_GELU) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] += bias[jp][e];
         if (p.drop_thr) {
@@ -1097,8 +1149,13 @@ PVR_DEV void epilogue_direct(const GemmParams& p, v4f (&acc)[8][4], char* smem, 
         }
       }
       v4u out;
-      if constexpr (EPI == EPI_BF16) {
-        if (p.drop_thr) {
+      if constexpr (epi_bf16(EPI)) {
+        if constexpr (EPI == EPI_BF16_DP) {  // (see `epilogue`: -0 keeps a dropped row's residual bits)
+          const bool rk = rf != 0.f;
+          const float zero = rk ? 0.f : -0.f;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) v[e] = keep[e] && rk ? v[e] * rf : zero;
+        } else if (p.drop_thr) {
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = keep[e] ? v[e] * p.drop_scale : 0.f;
         }
@@ -1237,7 +1294,7 @@ PVR_DEV void epilogue_staged(const GemmParams& p, v4f (&acc)[8][4], char* smem, 
   const int n = n0 + 4 * cq;
   const bool ncol = n < p.N;
   float4 bias = make_float4(0.f, 0.f, 0.f, 0.f);
-  if constexpr (EPI == EPI_BF16 || EPI == EPI_GELU) {
+  if constexpr (epi_bf16(EPI) || EPI == EPI_GELU) {
     if (p.bias && ncol) bias = *(const float4*)(p.bias + n);
   }
   const uint64_t seed = (p.drop_thr ? *p.seed_ptr : 0ull) + p.seed_offset;
@@ -1245,6 +1302,8 @@ PVR_DEV void epilogue_staged(const GemmParams& p, v4f (&acc)[8][4], char* smem, 
   // every dropout element index of the tensor fits in 32 bits (the usual case): 32-bit hash path
   const bool idx32 = (uint64_t)p.M * (uint64_t)p.N + 4 <= 0xFFFFFFFFull;
   const float deq = p.scale_a ? (*p.scale_a) * (*p.scale_b) : 1.f;
+  DpRowScale dps{};  // drop path (EPI_BF16_DP): see epilogue_direct
+  if constexpr (EPI == EPI_BF16_DP) dps.init(p, m0);
   float csum[4] = {0.f, 0.f, 0.f, 0.f};
   constexpr int NPASS = 256 / RP, FPP = RP / 16;  // passes; fragment rows (of 8 per wave) per pass
 #pragma unroll
@@ -1293,7 +1352,7 @@ PVR_DEV void epilogue_staged(const GemmParams& p, v4f (&acc)[8][4], char* smem, 
     // (rows / columns clamped into range): a load under a per-row branch makes the compiler wait
     // vmcnt(0) after each one, serialising them and draining every in-flight LDS-DMA.
     constexpr int RPT = RP / 8;  // rows per thread per pass
-    constexpr bool HAS_IN = EPI == EPI_DGELU || (EPI == EPI_BF16 && RES);
+    constexpr bool HAS_IN = EPI == EPI_DGELU || (epi_bf16(EPI) && RES);
     // Row k of this thread is mrow0 + 8k: every per-row address and the dropout element index are
     // a base plus k times a wave-uniform step, so no 64-bit multiply (quarter rate) runs per row.
     const int mrow0 = m0 + half * RP + (tid >> 6);
@@ -1322,7 +1381,7 @@ PVR_DEV void epilogue_staged(const GemmParams& p, v4f (&acc)[8][4], char* smem, 
       const v4f a = *(const v4f*)(smem + r * 1024 + ((cq ^ (r & 63)) << 4));
       const bool ok = m < p.M && ncol;
       float v[4] = {a[0] * deq, a[1] * deq, a[2] * deq, a[3] * deq};
-      if constexpr (EPI == EPI_BF16 || EPI == EPI_GELU) {
+      if constexpr (epi_bf16(EPI) || EPI == EPI_GELU) {
         v[0] += bias.x; v[1] += bias.y; v[2] += bias.z; v[3] += bias.w;
         bool keep[4] = {true, true, true, true};
         if (p.drop_thr) {
@@ -1334,8 +1393,14 @@ PVR_DEV void epilogue_staged(const GemmParams& p, v4f (&acc)[8][4], char* smem, 
             rng_keep2(seed, idx + 2, p.drop_thr, keep[2], keep[3]);
           }
         }
-        if constexpr (EPI == EPI_BF16) {
-          if (p.drop_thr) {
+        if constexpr (epi_bf16(EPI)) {
+          if constexpr (EPI == EPI_BF16_DP) {  // (see `epilogue`: -0 keeps a dropped row's residual bits)
+            const float rf = dps.factor(p, m);
+            const bool rk = rf != 0.f;
+            const float zero = rk ? 0.f : -0.f;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = keep[q] && rk ? v[q] * rf : zero;
+          } else if (p.drop_thr) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) v[q] = keep[q] ? v[q] * p.drop_scale : 0.f;
           }
@@ -1673,7 +1738,7 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(GemmParams p) {
     for (int k = 0; k < 8; ++k) p.dbg[(b * 8 + wave) * 8 + k] = pst.acc[k];
   }
 #endif
-  if constexpr (EPI == EPI_BF16 || EPI == EPI_GELU || EPI == EPI_DGELU) {
+  if constexpr (epi_bf16(EPI) || EPI == EPI_GELU || EPI == EPI_DGELU) {
     if (tpart >= 0 && !tail_gather(p, acc, smem, tloc, tpart)) return;  // another part finishes the tile
   }
   if constexpr (SWAP && (EPI == EPI_F32_ATOMIC || EPI == EPI_F32_STORE)) {
@@ -1684,17 +1749,19 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(GemmParams p) {
     if constexpr (EPI == EPI_F32_STORE) {
       if (p.sk_out) splitk_fixup(p, smem, tt, m0, n0);  // host: staged path (N % 4 == 0, no row groups)
     }
-  } else if constexpr (SWAP && (EPI == EPI_BF16 || EPI == EPI_GELU || EPI == EPI_DGELU)) {
+  } else if constexpr (SWAP && (epi_bf16(EPI) || EPI == EPI_GELU || EPI == EPI_DGELU)) {
     if (!p.epi_staged && direct_ok(p)) {
       // (one instance per epilogue actually reachable: a residual exists for BF16 only; a second,
-      // identical GELU / dGELU copy doubled the kernel's code, and its hot path's I-cache footprint)
-      if (EPI == EPI_BF16 && p.resid)
-        epilogue_direct<EPI, EPI == EPI_BF16, ES == 1>(p, acc, smem, m0 + wm * 128, n0 + wn * 64, wm, wn, lane);
+      // identical GELU / dGELU copy doubled the kernel's code, and its hot path's I-cache footprint.
+      // EPI_BF16_DP: pvr_gemm guarantees a residual, no addend / row_group and N % 8 == 0, so only
+      // the two residual instances exist there: the other branches fold away)
+      if (EPI == EPI_BF16_DP || (epi_bf16(EPI) && p.resid))
+        epilogue_direct<EPI, epi_bf16(EPI), ES == 1>(p, acc, smem, m0 + wm * 128, n0 + wn * 64, wm, wn, lane);
       else
         epilogue_direct<EPI, false, ES == 1>(p, acc, smem, m0 + wm * 128, n0 + wn * 64, wm, wn, lane);
-    } else if (!p.addend && !p.row_group && (p.N & 3) == 0) {
-      if (EPI == EPI_BF16 && p.resid)
-        epilogue_staged<EPI, 128, EPI == EPI_BF16>(p, acc, smem, m0, n0, wm, wn, lane);
+    } else if (EPI == EPI_BF16_DP || (!p.addend && !p.row_group && (p.N & 3) == 0)) {
+      if (EPI == EPI_BF16_DP || (epi_bf16(EPI) && p.resid))
+        epilogue_staged<EPI, 128, epi_bf16(EPI)>(p, acc, smem, m0, n0, wm, wn, lane);
       else
         epilogue_staged<EPI, 128, false>(p, acc, smem, m0, n0, wm, wn, lane);
     }
@@ -1754,7 +1821,7 @@ hipError_t launch_pp(const GemmParams& p, hipStream_t s) {
   GemmParams q = p;
   q.tail_from = q.tail_split = 0;
   int grid = ntm * ntn;
-  if constexpr (AK && BKC && (EPI == EPI_BF16 || EPI == EPI_GELU || EPI == EPI_DGELU)) {
+  if constexpr (AK && BKC && (epi_bf16(EPI) || EPI == EPI_GELU || EPI == EPI_DGELU)) {
     if (nsplit == 1) {
       plan_tail(q, ntm * ntn, 128 / ES);
       grid = tail_grid(TailPlan{q.tail_from, q.tail_split}, ntm * ntn);
@@ -1901,7 +1968,7 @@ __global__ void __launch_bounds__(512, 2) gemm_ppp_kernel(GemmParams p) {
   // epilogue stores per wave left in flight across the tile boundary (0: drain): the register-direct
   // BF16 epilogue issues 16 x 16 B, GELU 32 (output + derivative), dGELU 16 + 8 column-sum atomics
   // (to a 0-byte resource without colsum)
-  constexpr int INFL = !DIRECT ? 0 : EPI == EPI_BF16 ? 16 : EPI == EPI_GELU ? 32 : 24;
+  constexpr int INFL = !DIRECT ? 0 : epi_bf16(EPI) ? 16 : EPI == EPI_GELU ? 32 : 24;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1977,13 +2044,13 @@ __global__ void __launch_bounds__(512, 2) gemm_ppp_kernel(GemmParams p) {
     // registers (DIRECT; the DGELU column-sum exchange uses the separate region) or stages in the
     // separate region behind them.
     if constexpr (DIRECT) {
-      if (EPI == EPI_BF16 && p.resid)  // (see gemm_pp_kernel: one instance per reachable epilogue)
-        epilogue_direct<EPI, EPI == EPI_BF16, ES == 1>(p, acc, smem + 2 * PP_BUF, cur.m0 + wm * 128, cur.n0 + wn * 64, wm, wn, lane);
+      if (EPI == EPI_BF16_DP || (epi_bf16(EPI) && p.resid))  // (see gemm_pp_kernel: one instance per reachable epilogue)
+        epilogue_direct<EPI, epi_bf16(EPI), ES == 1>(p, acc, smem + 2 * PP_BUF, cur.m0 + wm * 128, cur.n0 + wn * 64, wm, wn, lane);
       else
         epilogue_direct<EPI, false, ES == 1>(p, acc, smem + 2 * PP_BUF, cur.m0 + wm * 128, cur.n0 + wn * 64, wm, wn, lane);
     } else if constexpr (ES == 2) {
-      if (EPI == EPI_BF16 && p.resid)
-        epilogue_staged<EPI, 32, EPI == EPI_BF16>(p, acc, smem + 2 * PP_BUF, cur.m0, cur.n0, wm, wn, lane);
+      if (EPI == EPI_BF16_DP || (epi_bf16(EPI) && p.resid))
+        epilogue_staged<EPI, 32, epi_bf16(EPI)>(p, acc, smem + 2 * PP_BUF, cur.m0, cur.n0, wm, wn, lane);
       else
         epilogue_staged<EPI, 32, false>(p, acc, smem + 2 * PP_BUF, cur.m0, cur.n0, wm, wn, lane);
     }
@@ -2040,7 +2107,7 @@ hipError_t launch_tile(const GemmParams& p, hipStream_t s) {
   switch (p.tile_cfg) {
     case 6: return launch_v3<256, 256, 2, 4, 4, 2, AK, BKC, SWAP, EPI>(p, s);
     case 13:  // persistent ping-pong (k-contiguous bf16, bf16-output epilogues, no split-K)
-      if constexpr (AK && BKC && SWAP && (EPI == EPI_BF16 || EPI == EPI_GELU || EPI == EPI_DGELU)) {
+      if constexpr (AK && BKC && SWAP && (epi_bf16(EPI) || EPI == EPI_GELU || EPI == EPI_DGELU)) {
         if (p.K % PP_BK == 0 && p.K >= 2 * PP_BK && p.k_split_len >= p.K && !p.addend && !p.row_group && (p.N & 3) == 0)
           return launch_ppp<SWAP, EPI>(p, s);
       }
@@ -2087,6 +2154,17 @@ extern "C" hipError_t pvr_gemm(const pvr::GemmParams* pp, hipStream_t s) {
   if (p.M <= 0 || p.N <= 0 || p.K <= 0) return hipSuccess;
   // compact class-token rows with the full tensor's dropout mask: the shared epilogue of the 128x128 tiles
   if (p.drop_row_mul && (p.drop_row_mul < 0 || p.tile_cfg != 0 || p.row_group || p.elem8)) return hipErrorInvalidValue;
+  if (p.epi < EPI_BF16 || p.epi > EPI_F32_STORE) return hipErrorInvalidValue;  // EPI_BF16_DP is chosen here, not passed
+  // drop path: the residual forward GEMMs (k-contiguous bf16 operands) on tiles 0, 6, 12 and 13.
+  // N % 8 == 0: the ping-pong kernels take the staged epilogue (4-column groups) for EPI_BF16_DP
+  // without the N % 4 test of the other epilogues
+  if (p.dp_thr) {
+    const bool tile_ok = p.tile_cfg == 0 || p.tile_cfg == 6 || p.tile_cfg == 12 || p.tile_cfg == 13;
+    if (p.epi != EPI_BF16 || !p.resid || !p.seed_ptr || p.dp_rows < 1 || p.dp_thr > 65535u || p.elem8 || p.row_group || p.addend ||
+        (p.N & 7) || !tile_ok || !p.a_kcontig || !p.b_kcontig || p.k_split_len < p.K)
+      return hipErrorInvalidValue;
+    return launch_tile<true, true, true, EPI_BF16_DP>(p, s);
+  }
   // tile 15: wave-specialized persistent kernel (epilogue waves beside the MFMA waves); shapes it
   // does not take fall through to the 256x256 ping-pong
   if (p.tile_cfg == 15) {

@@ -61,6 +61,14 @@ struct GemmParams {
   // that of row m * drop_row_mul there, while loads and stores use m. The 128x128 tiles (tile_cfg 0)
   // only; without row_group.
   int drop_row_mul;
+  // Stochastic depth (drop path) of EPI_BF16's residual branch, dp_thr > 0 (0: off): output row
+  // orow belongs to sample b = orow / dp_rows (dp_rows = tokens per image for a token matrix, 1 for
+  // compact class-token rows); the sample's branch is kept iff rng_keep(*seed_ptr + dp_seed_offset,
+  // b, dp_thr) and then scaled by dp_scale = 65536 / (65536 - dp_thr):
+  //   out = resid + s[b] * dropout(acc + bias),  s[b] = 0 or dp_scale
+  // (a dropped row's output is its residual bit for bit). Needs resid and seed_ptr; bf16 operands,
+  // no row_group / addend; tiles 0, 6, 12, 13.
+  uint32_t dp_thr; float dp_scale; uint64_t dp_seed_offset; int dp_rows;
 };
 
 }  // namespace pvr

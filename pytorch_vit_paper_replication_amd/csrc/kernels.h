@@ -34,6 +34,12 @@ struct DropSite {
   const uint64_t* seed = nullptr; uint64_t offset = 0; uint32_t thr = 0; float scale = 1.f;
 };
 
+// A drop-path (stochastic depth) site is a DropSite too, drawn per sample instead of per element:
+// sample b is kept iff its 16-bit hash of (*seed + offset), index b, is >= thr, and a kept sample's
+// residual branch scales by `scale`: s[b] = 0 or scale. A kernel takes it with dp_rows, the rows per
+// sample (row r belongs to sample r / dp_rows). Sites: DROP_PATH_SITE + 2 i (attention branch of
+// block i) and + 2 i + 1 (MLP branch), ops/fused_vit.py.
+
 // Optional fp8 copy of a kernel's output (producer-side quantization of the delayed-scaling recipe):
 // out[r][c] = fp8(v * (*scale)) (fmt 0 e4m3, 1 e5m2; row stride ld bytes), *amax = max(*amax, max|v|)
 // (float bits). out null: none.
@@ -69,10 +75,13 @@ struct LnBwdParams {
   int dres_every;
   uint16_t* dx; int64_t dx_stride;
   float* dw; float* db; float* dsum;
-  // dz (optional, needs drop.seed): dz = mask * scale * dx, the dropout backward of the layer that
-  // produced x's residual stream; dsum then receives dz's column sums. dz_nostore: only dz's fp8
-  // copy is written (needs q.out).
+  // dz (optional, needs drop.seed or dpath.seed): dz = s[row / dp_rows] * mask * scale * dx, the
+  // dropout and / or drop-path backward of the branch that produced x's residual stream (either
+  // factor alone is legal); dsum then receives dz's column sums. dz_nostore: only dz's fp8 copy is
+  // written (needs q.out).
   uint16_t* dz; int64_t dz_stride; DropSite drop; int dz_nostore;
+  // drop path of that branch (a per-sample DropSite, see above; seed null: none; not with the fp8 copy q)
+  DropSite dpath; int dp_rows;
   Fp8Copy q;  // copy of the last-written gradient (dz if given, else dx); row stride and base % 8
   int rows, D;
   float* part;  // deterministic mode: [pvr_layernorm_bwd_blocks][3][D] partial rows (null: atomics)
@@ -145,9 +154,14 @@ int pvr_colsum_part_rows(int rows);
 // db (optional) += column sums of dy, or of dz = mask * scale * dy when drop.seed is set; dz
 // (optional) receives that product, q its fp8 copy (row stride and base % 8); part: deterministic
 // mode scratch [pvr_colsum_part_rows][N]; row_mul >= 1: row r takes the dropout mask of row r * row_mul
-// (the compact class-token rows of a [rows * row_mul][N] tensor)
+// (the compact class-token rows of a [rows * row_mul][N] tensor). dpath (seed null: none): the branch's
+// drop-path site, dz = s[r / dp_rows] * mask * scale * dy (independent of row_mul: compact rows are
+// samples, dp_rows = 1); not with the fp8 copy
 hipError_t pvr_colsum(const uint16_t* dy, int64_t ld, int rows, int N, float* db, uint16_t* dz, int64_t ld_dz, pvr::DropSite drop,
-                      pvr::Fp8Copy q, float* part, int row_mul, hipStream_t s);
+                      pvr::Fp8Copy q, float* part, int row_mul, pvr::DropSite dpath, int dp_rows, hipStream_t s);
+// s [B] f32 = the drop-path scale vector of a site (0 or dpath.scale per sample): diagnostics and the
+// torch fallback's replay of the kernels' draws
+hipError_t pvr_drop_path_scale(pvr::DropSite dpath, float* s_out, int B, hipStream_t s);
 // d0/d1/d2[c % seg] += sum over the R rows of part[R][C] (row order: deterministic)
 hipError_t pvr_rows_reduce(const float* part, int R, int C, int seg, float* d0, float* d1, float* d2, hipStream_t s);
 // mix (both patchify kernels; null: none): the batch's MixRow plan, host-validated (bindings.cpp mix_rows)

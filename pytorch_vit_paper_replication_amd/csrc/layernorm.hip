@@ -206,7 +206,12 @@ struct RowVec<4> {
 // Q8: the fp8-copy variant (qout / dz_nostore used); the bf16 instantiation carries none of it.
 // SP: the residual gradient exists on every dres_every-th row only (the class-token rows), read from
 // the compact dres [rows / dres_every][D]; the other rows get LN'(dy) alone.
-template <int MAXCH, int W, bool Q8, bool SP>
+// DP: dz carries the drop-path row scale of the branch as well, dz = s[row / dp_rows] * mask * scale * dx
+// with s = 0 or dp_scale per sample (DropSite dpath in kernels.h); thr == 0 then means no element
+// dropout (dz = s * dx). A row is one wave's, so the draw is wave-uniform: one hash per row. The
+// element scale and the row scale are folded into one fp32 factor, as in the GEMM epilogue that
+// applied them forward. The instantiations without DP carry none of it.
+template <int MAXCH, int W, bool Q8, bool SP, bool DP = false>
 __global__ void __launch_bounds__(256) ln_bwd_kernel(const uint16_t* __restrict__ dy, int64_t dy_stride,
                                                       const uint16_t* __restrict__ x, int64_t x_stride,
                                                       const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -219,7 +224,9 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const uint16_t* __restrict_
                                                       const uint64_t* __restrict__ seed_ptr, uint64_t seed_off, uint32_t thr,
                                                       float dscale, int dz_nostore, uint8_t* __restrict__ qout, int64_t q_stride,
                                                       const float* __restrict__ qscale, unsigned* __restrict__ amax, int qfmt,
-                                                      int rows, int D, int dres_every) {
+                                                      int rows, int D, int dres_every,
+                                                      const uint64_t* __restrict__ dp_seed_ptr, uint64_t dp_off, uint32_t dp_thr,
+                                                      float dp_scale, int dp_rows) {
   __shared__ float red[4][MAXCH * 64 * W > 1280 ? 1280 : MAXCH * 64 * W];  // one partial at a time
   __shared__ float qred[4];
   const float qs = Q8 ? *qscale : 1.f;
@@ -265,7 +272,13 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const uint16_t* __restrict_
       wreg[i][j] = w4.x; wreg[i][j + 1] = w4.y; wreg[i][j + 2] = w4.z; wreg[i][j + 3] = w4.w;
     }
   }
-  const uint64_t seed = dz ? *seed_ptr + seed_off : 0ull;
+  const uint64_t seed = dz && (!DP || thr) ? *seed_ptr + seed_off : 0ull;
+  uint32_t dkey = 0u;
+  float dfk = 0.f;
+  if constexpr (DP) {
+    dkey = rng_key(*dp_seed_ptr + dp_off);
+    dfk = (thr ? dscale : 1.f) * dp_scale;
+  }
   int row = blockIdx.x * 4 + wave;
   load_row(row, cx, cdy, cr);
   float cmu = row < rows ? mean[row] : 0.f, crs = row < rows ? rstd[row] : 0.f;
@@ -312,17 +325,40 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const uint16_t* __restrict_
         for (int j = 0; j < W; j += 2) q.u[j >> 1] = pack2bf(o[j], o[j + 1]);
         q.store(dx + (int64_t)row * dx_stride + c * W);
         if (dz) {  // uniform: dropout backward of the producing layer
+          if constexpr (DP) {
+            const float rf = rng_keep_32(dkey, (uint32_t)row / (uint32_t)dp_rows, dp_thr) ? dfk : 0.f;  // wave-uniform
 #pragma unroll
-          for (int j = 0; j < W; j += 2) {
-            bool k0, k1;
-            rng_keep2(seed, (uint64_t)row * D + c * W + j, thr, k0, k1);
-            o[j] = k0 ? o[j] * dscale : 0.f;
-            o[j + 1] = k1 ? o[j + 1] * dscale : 0.f;
+            for (int j = 0; j < W; j += 2) {
+              bool k0 = true, k1 = true;
+              if (thr) rng_keep2(seed, (uint64_t)row * D + c * W + j, thr, k0, k1);
+              o[j] = k0 ? o[j] * rf : 0.f;
+              o[j + 1] = k1 ? o[j + 1] * rf : 0.f;
+            }
+          } else {
+#pragma unroll
+            for (int j = 0; j < W; j += 2) {
+              bool k0, k1;
+              rng_keep2(seed, (uint64_t)row * D + c * W + j, thr, k0, k1);
+              o[j] = k0 ? o[j] * dscale : 0.f;
+              o[j + 1] = k1 ? o[j + 1] * dscale : 0.f;
+            }
           }
           if (!Q8 || !dz_nostore) {  // uniform; dz_nostore: only dz's e5m2 copy (qout) is consumed
 #pragma unroll
             for (int j = 0; j < W; j += 2) q.u[j >> 1] = pack2bf(o[j], o[j + 1]);
             q.store(dz + (int64_t)row * dz_stride + c * W);
+          }
+          if constexpr (DP) {
+            // With drop path, dsum sums the bf16 values of dz just stored, not their fp32 precursors as
+            // the other instantiations do. dsum is the bias gradient (d(bo), d(b2)) of a branch whose
+            // weight gradient and dgrad are GEMMs over that bf16 dz: defined as the column sums of the
+            // tensor dz itself, all three gradients of the branch come from one tensor, and
+            // dsum == dz.sum(0) holds up to the order of the adds (which the tests use). The drop-path
+            // instantiation of colsum_kernel (elementwise.hip), which does this for the last block, sums
+            // the same way. The fp32 sum differs by the bf16 rounding of each element (up to 2^-9
+            // relative per element); the instantiations without drop path keep the fp32 sum they had.
+#pragma unroll
+            for (int j = 0; j < W; ++j) o[j] = bf2f(j & 1 ? q.u[j >> 1] >> 16 : q.u[j >> 1] & 0xFFFF);
           }
         }
         if constexpr (Q8) {  // fp8 copy (qfmt 1 e5m2, 0 e4m3) of the gradient written last (dz, else dx) for the next fp8 dgrad GEMM
@@ -466,7 +502,12 @@ extern "C" hipError_t pvr_layernorm_bwd(const pvr::LnBwdParams* pp, hipStream_t 
   const int rows = p.rows, D = p.D;
   if (rows <= 0) return hipSuccess;
   if (q.fmt != 0 && q.fmt != 1) return hipErrorInvalidValue;
-  if (D % 8 != 0 || D > 1280 || (p.dz && (!d.seed || !d.thr))) return hipErrorInvalidValue;
+  const DropSite& dp = p.dpath;
+  const bool has_drop = d.seed && d.thr, has_dp = dp.seed && dp.thr;
+  // dz is the backward of element dropout, of drop path, or of both: at least one of them
+  if (D % 8 != 0 || D > 1280 || (p.dz && !has_drop && !has_dp)) return hipErrorInvalidValue;
+  // drop path: a dz output of the bf16 kernels (the fp8 gradient copies would have to be taken from dz)
+  if (has_dp && (!p.dz || q.out || p.dp_rows < 1 || dp.thr > 65535u)) return hipErrorInvalidValue;
   if (q.out && (!q.scale || !q.amax || q.ld % 8 != 0 || reinterpret_cast<uintptr_t>(q.out) % 8 != 0)) return hipErrorInvalidValue;
   if (p.dz_nostore && (!p.dz || !q.out)) return hipErrorInvalidValue;  // skipping dz needs dz's fp8 copy
   // residual gradient on every dres_every-th row only (compact dres): the bf16 kernels
@@ -483,9 +524,9 @@ extern "C" hipError_t pvr_layernorm_bwd(const pvr::LnBwdParams* pp, hipStream_t 
   float* part = p.dw || p.db || p.dsum ? p.part : nullptr;
   const dim3 grid(nblk), block(256);
 #define PVR_LN_BWD(MC, W)                                                                                                   \
-  hipLaunchKernelGGL(q.out ? (ln_bwd_kernel<MC, W, true, false>) : sparse ? (ln_bwd_kernel<MC, W, false, true>) : (ln_bwd_kernel<MC, W, false, false>), grid, block, 0, s, p.dy, p.dy_stride, p.x, p.x_stride, p.mean, p.rstd, p.w, p.dres, p.dres_stride, p.dx, \
+  hipLaunchKernelGGL(q.out ? (ln_bwd_kernel<MC, W, true, false>) : has_dp ? (sparse ? (ln_bwd_kernel<MC, W, false, true, true>) : (ln_bwd_kernel<MC, W, false, false, true>)) : sparse ? (ln_bwd_kernel<MC, W, false, true>) : (ln_bwd_kernel<MC, W, false, false>), grid, block, 0, s, p.dy, p.dy_stride, p.x, p.x_stride, p.mean, p.rstd, p.w, p.dres, p.dres_stride, p.dx, \
                      p.dx_stride, p.dw, p.db, p.dsum, part, p.dz, p.dz_stride, d.seed, d.offset, d.thr, d.scale, p.dz_nostore, q.out, q.ld, q.scale, q.amax, \
-                     q.fmt, rows, D, p.dres_every)
+                     q.fmt, rows, D, p.dres_every, dp.seed, dp.offset, has_dp ? dp.thr : 0u, dp.scale, p.dp_rows)
   if (use_w4) {
     switch (D / 256) {
       case 3: PVR_LN_BWD(3, 4); break;  // D = 768

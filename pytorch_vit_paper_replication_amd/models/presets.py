@@ -15,10 +15,16 @@ PRESETS: Dict[str, Dict] = {
 }
 
 
-def vit(name: str, image_size: int = 224, num_classes: int = 1000, **overrides) -> ViT:
+def vit(name: str, image_size: int = 224, num_classes: int = 1000, drop_path: float = 0.0,
+        drop_path_schedule: str = "linear", **overrides) -> ViT:
+    """``drop_path`` > 0: stochastic depth at that rate (:meth:`ViT.set_drop_path`; the from-scratch recipes
+    use 0.1 for ViT-B and more for ViT-L / ViT-H)."""
     cfg = dict(PRESETS[name])
     cfg.update(overrides)
-    return ViT(image_size=image_size, num_classes=num_classes, **cfg)
+    model = ViT(image_size=image_size, num_classes=num_classes, **cfg)
+    if drop_path:
+        model.set_drop_path(drop_path, drop_path_schedule)
+    return model
 
 
 def vit_b16(**kw) -> ViT:

@@ -152,8 +152,37 @@ class MLPBlock(nn.Module):
         return self.mlp(self.layer_norm(x))
 
 
+def drop_path_thr(p: float) -> int:
+    """The 16-bit threshold of a drop rate, as at every dropout site of the fused kernels:
+    ``min(round(p * 65536), 65535)`` (halves round up, as the host code of the kernels rounds); a sample
+    is kept iff its 16-bit draw is ``>= thr``. A rate below ``2 ** -17`` has threshold 0: it never drops."""
+    return min(int(math.floor(float(p) * 65536.0 + 0.5)), 65535)
+
+
+def drop_path_keep_scale(p: float) -> float:
+    """What a kept branch is multiplied by: ``65536 / (65536 - thr)`` (fp32 in the kernels)."""
+    return 65536.0 / (65536.0 - drop_path_thr(p))
+
+
+def drop_path_rates(rate: float, depth: int, schedule: str = "linear"):
+    """Per-block drop-path rates: ``rate * i / (depth - 1)`` (``rate`` for a single block), or ``rate``
+    for every block with ``schedule="constant"``."""
+    if schedule not in ("linear", "constant"):
+        raise ValueError(f"drop-path schedule must be 'linear' or 'constant', got {schedule!r}")
+    rate = float(rate)
+    if not 0.0 <= rate < 1.0:
+        raise ValueError(f"drop-path rate must be in [0, 1), got {rate}")
+    if schedule == "constant" or depth <= 1:
+        return [rate] * depth
+    return [rate * i / (depth - 1) for i in range(depth)]
+
+
 class TransformerEncoderBlock(nn.Module):
-    """x = MSA(x) + x ; x = MLP(x) + x (reference models/vit.py:133-169)."""
+    """x = MSA(x) + x ; x = MLP(x) + x (reference models/vit.py:133-169).
+
+    ``drop_path`` (attribute, default 0; set by :meth:`ViT.set_drop_path`): stochastic depth. In training
+    each sample drops each of the two residual branches independently with this probability, and a
+    kept branch is scaled by ``drop_path_keep_scale``: ``x = x + s[b] * branch(x)``."""
 
     def __init__(self, embedding_dim: int = 768, num_heads: int = 12, attn_dropout: float = 0,
                  mlp_size: int = 3072, mlp_dropout: float = 0.1):
@@ -161,11 +190,27 @@ class TransformerEncoderBlock(nn.Module):
         self.msa_block = MultiHeadSelfAttentionBlock(embedding_dim=embedding_dim, num_heads=num_heads,
                                                      attn_dropout=attn_dropout)
         self.mlp_block = MLPBlock(embedding_dim=embedding_dim, mlp_size=mlp_size, dropout=mlp_dropout)
+        self.drop_path = 0.0
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        x = self.msa_block(x) + x
-        x = self.mlp_block(x) + x
+        p = self.drop_path if self.training else 0.0
+        if p <= 0.0 or drop_path_thr(p) == 0:
+            x = self.msa_block(x) + x
+            x = self.mlp_block(x) + x
+            return x
+        x = self._drop_path_scale(x, p, 0) * self.msa_block(x) + x
+        x = self._drop_path_scale(x, p, 1) * self.mlp_block(x) + x
         return x
+
+    def _draw_drop_path(self, batch: int, p: float, branch: int, device) -> torch.Tensor:
+        """Keep decisions (bool ``[batch]``) of one residual branch (0 attention, 1 MLP) on the reference
+        path: 16-bit draws from torch's RNG against the kernels' threshold."""
+        return torch.randint(0, 65536, (batch,), device=device) >= drop_path_thr(p)
+
+    def _drop_path_scale(self, x: torch.Tensor, p: float, branch: int) -> torch.Tensor:
+        """``s[b]`` as ``[B, 1, 1]`` in x's dtype: 0 for a dropped sample, else ``drop_path_keep_scale(p)``."""
+        keep = self._draw_drop_path(x.shape[0], p, branch, x.device)
+        return (keep.to(device=x.device, dtype=x.dtype) * drop_path_keep_scale(p)).view(-1, 1, 1)
 
     # fused-path helpers ---------------------------------------------------------------
     def fused_params(self):
@@ -212,6 +257,30 @@ class ViT(nn.Module):
         x = self._mix_reference(self._preprocess_reference(x, pre), mix)
         x = self.forward_features(x)
         return self.classifier(x[:, 0])
+
+    # ------------------------------------------------------------------ stochastic depth
+    def set_drop_path(self, rate: float, schedule: str = "linear") -> "ViT":
+        """Stochastic depth (drop path; Huang et al. 2016, the DeiT / ViT from-scratch recipes): in training,
+        each sample drops each residual branch of block ``i`` independently with probability ``p_i`` and
+        a kept branch is scaled by ``1 / (1 - p_i)``; ``p_i = rate * i / (L - 1)`` (``schedule="linear"``,
+        ``p_0 = 0``; ``rate`` itself for a single block) or ``rate`` for every block (``"constant"``).
+        Eval and inference never drop. ``rate = 0`` turns it off: the model then runs exactly as before.
+
+        On the fused path the keep decisions come from the counter hash of the dropout masks (sites
+        ``DROP_PATH_SITE + 2 i`` / ``+ 2 i + 1``, the step's value of the device counter), inside the
+        out-projection and fc2 GEMM epilogues; elsewhere the same formula draws from torch's RNG. Not
+        with :meth:`enable_fp8`. The constructor signature and ``state_dict()`` are unchanged; the rate
+        is kept in ``config["drop_path"]`` (and the schedule in ``config["drop_path_schedule"]``)."""
+        rates = drop_path_rates(rate, len(self.transformer_encoder), schedule)
+        for blk, p in zip(self.transformer_encoder, rates):
+            blk.drop_path = p
+        self.config["drop_path"] = float(rate)
+        self.config["drop_path_schedule"] = schedule
+        return self
+
+    def drop_path_rates(self):
+        """The per-block rates in effect (all 0 without :meth:`set_drop_path`)."""
+        return [float(getattr(blk, "drop_path", 0.0)) for blk in self.transformer_encoder]
 
     # ------------------------------------------------------------------ uint8 input
     def set_device_input(self, spec) -> "ViT":
@@ -330,12 +399,18 @@ class ViT(nn.Module):
         class-token rows alone (ops/fused_vit.py ``CLS_LAST_BLOCK``), and ``tokens`` is then ``[B, D]``.
         ``pre`` = ``(mean, std, geom)`` of a uint8 batch (:meth:`_device_input`), None for a float one.
         ``mix``: the batch's ``MixPlan`` (None: none), applied by the patchify kernel."""
-        from ..ops.fused_vit import (ATTN_SITE, EncoderBlockClsFn, EncoderBlockFn, PatchEmbedFn, PatchEmbedU8Fn, block_links,
-                                     cls_last_block_ok, site_drop)
+        from ..ops.fused_vit import (ATTN_SITE, DROP_PATH_SITE, EncoderBlockClsFn, EncoderBlockFn, PatchEmbedFn, PatchEmbedU8Fn,
+                                     block_links, cls_last_block_ok, site_drop)
         from ..runtime.param_store import get_store
 
         c = self.config
         dev = x.device
+        # (a rate whose 16-bit threshold is 0 never drops and scales by 1: such a block runs as one without)
+        dp_rates = [p if self.training and drop_path_thr(p) > 0 else 0.0 for p in self.drop_path_rates()]
+        if any(p > 0 for p in dp_rates) and getattr(self, "_fp8_cfg", None) is not None:
+            raise NotImplementedError(
+                "enable_fp8() does not combine with set_drop_path(): the fp8 gradient copies of the out-projection and "
+                "fc2 dgrads would have to be taken from the drop-path-scaled gradients; turn one of the two off")
         for p in self.parameters():
             if p.device != dev:
                 raise RuntimeError(f"input is on {dev} but model parameters are on {p.device}")
@@ -351,7 +426,8 @@ class ViT(nn.Module):
         store.grad_enabled = grad  # the fused Functions' forward runs with grad mode off: tell them
         if grad:
             store.prepare_grads()
-        need_seed = training and (c["mlp_dropout"] > 0 or c["embedding_dropout"] > 0 or c["attn_dropout"] > 0)
+        need_seed = training and (c["mlp_dropout"] > 0 or c["embedding_dropout"] > 0 or c["attn_dropout"] > 0
+                                  or any(p > 0 for p in dp_rates))
         seed = self._dropout_seed(dev) if need_seed else None
         pe = self.patch_embedding_block
         conv = pe.patch_and_flatten[0]
@@ -370,13 +446,17 @@ class ViT(nn.Module):
             f8.begin_step(training)
         blocks = list(self.transformer_encoder)
         drops2 = [site_drop(seed, 2 + 2 * i, blk.mlp_block.mlp[4].p, training) for i, blk in enumerate(blocks)]
-        links = block_links(blocks, drops2)
+        # drop path: the MLP-branch site of block i rides in its link (the next block's LayerNorm backward applies it)
+        dps2 = [site_drop(seed, DROP_PATH_SITE + 2 * i + 1, dp_rates[i], training) for i in range(len(blocks))]
+        links = block_links(blocks, drops2, dps2)
         for i, blk in enumerate(blocks):
             ln1 = blk.msa_block.layer_norm
             ln2 = blk.mlp_block.layer_norm
             mha = blk.msa_block.multi_head_attention
             drops = (site_drop(seed, 1 + 2 * i, blk.mlp_block.mlp[2].p, training), drops2[i],
                      site_drop(seed, ATTN_SITE + i, mha.dropout, training))
+            if dp_rates[i] > 0:  # rate 0: the 3-tuple of the code path without drop path
+                drops = drops + (site_drop(seed, DROP_PATH_SITE + 2 * i, dp_rates[i], training), dps2[i])
             if cls_rows and i == len(blocks) - 1 and cls_last_block_ok(N, mha.num_heads, c["embedding_dim"], f8, drops[2]):
                 tokens = EncoderBlockClsFn.apply(tokens, B, N, mha.num_heads, ln1.eps, ln2.eps, store, drops, links[i],
                                                  *blk.fused_params())

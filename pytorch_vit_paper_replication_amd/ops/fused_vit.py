@@ -25,6 +25,9 @@ from . import gemm
 
 SITE_SHIFT = 32
 ATTN_SITE = 1 << 20  # dropout site of block i's attention probabilities: ATTN_SITE + i
+# stochastic depth (drop path): block i's attention branch draws its per-sample keep decisions at site
+# DROP_PATH_SITE + 2 i, its MLP branch at DROP_PATH_SITE + 2 i + 1 (disjoint from 0 .. 2 L and ATTN_SITE + i)
+DROP_PATH_SITE = 1 << 21
 
 
 # Test hook: called as DGRAD_TAP(which, output) after every encoder-block dgrad GEMM (which = 0 fc2,
@@ -36,6 +39,19 @@ def site_drop(seed: Optional[torch.Tensor], site: int, p: float, training: bool)
     if seed is None or not training or p <= 0.0:
         return None
     return (seed, site << SITE_SHIFT, float(p))
+
+
+def _dp(site, rows: int):
+    """A drop-path site ``(seed, offset, p)`` (``site_drop`` of a DROP_PATH_SITE site; None: none) as the
+    ``drop_path`` argument of the GEMM / column-sum front ends, for a tensor with ``rows`` rows per sample."""
+    return None if site is None else (site[0], site[1], site[2], int(rows))
+
+
+def _split_drops(drops):
+    """(fc1 dropout, fc2 dropout, attention dropout, attention-branch drop path, MLP-branch drop path)
+    from a block's ``drops`` (the two drop-path sites are optional: a 3-tuple means none)."""
+    drops = tuple(drops)
+    return drops + (None,) * (5 - len(drops))
 
 
 def _patch_geometry(C, H, W, patch):
@@ -166,17 +182,20 @@ class BlockLink:
     """Backward hand-off between consecutive encoder blocks. Block i's final LayerNorm backward
     produces dx for block i-1 and, in the same pass, block i-1's fc2 dropout backward (dz2) and fc2
     bias gradient; block i-1's backward then starts from dz2 instead of re-reading dx with a
-    column-sum kernel."""
+    column-sum kernel. ``dp2``: block i-1's MLP-branch drop-path site, whose row scale the same pass
+    folds into dz2."""
 
-    __slots__ = ("drop2", "b2", "w2", "dz2", "dz2_q", "done")
+    __slots__ = ("drop2", "b2", "w2", "dz2", "dz2_q", "done", "dp2")
 
-    def __init__(self, drop2, b2, w2=None):
-        self.drop2, self.b2, self.w2, self.dz2, self.dz2_q, self.done = drop2, b2, w2, None, None, False
+    def __init__(self, drop2, b2, w2=None, dp2=None):
+        self.drop2, self.b2, self.w2, self.dz2, self.dz2_q, self.done, self.dp2 = drop2, b2, w2, None, None, False, dp2
 
 
-def block_links(blocks, drops2):
+def block_links(blocks, drops2, dps2=None):
     """(own link, previous block's link) per block, for EncoderBlockFn's ``links`` argument."""
-    own = [BlockLink(d, blk.mlp_block.mlp[3].bias, blk.mlp_block.mlp[3].weight) for blk, d in zip(blocks, drops2)]
+    dps2 = dps2 if dps2 is not None else [None] * len(drops2)
+    own = [BlockLink(d, blk.mlp_block.mlp[3].bias, blk.mlp_block.mlp[3].weight, dp)
+           for blk, d, dp in zip(blocks, drops2, dps2)]
     return [(own[i], own[i - 1] if i else None) for i in range(len(own))]
 
 
@@ -186,7 +205,11 @@ class EncoderBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, B, N, H, eps1, eps2, store, drops, f8, links, *params):
         ext = _ext.ext()
-        drop1, drop2, dropa = drops  # fc1 (after GELU), fc2, attention probabilities
+        # fc1 (after GELU), fc2, attention probabilities; drop path of the attention / MLP branch
+        drop1, drop2, dropa, dpa, dpm = _split_drops(drops)
+        if f8 is not None and (dpa is not None or dpm is not None):
+            raise NotImplementedError("enable_fp8() does not combine with set_drop_path(): the fp8 gradient copies "
+                                      "would have to be taken from the drop-path-scaled gradients")
         aseed, aoff, ap = gemm._drop_args(dropa)
         ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, w1, b1, w2, b2 = params
         T, D = x.shape
@@ -225,10 +248,10 @@ class EncoderBlockFn(torch.autograd.Function):
         if f8 is None:
             qkv = gemm.linear_fwd(xn1, store.bf16(wqkv), bqkv)
             o, lse = ext.attn_fwd(qkv, B, N, H, scale, aseed, aoff, ap)
-            x1 = gemm.linear_fwd(o, store.bf16(wo), bo, resid=x)
+            x1 = gemm.linear_fwd(o, store.bf16(wo), bo, resid=x, drop_path=_dp(dpa, N))
             xn2, mean2, rstd2 = ext.layernorm_fwd(x1, ln2w, ln2b, eps2, T, D)
             h = gemm.linear_fwd(xn2, store.bf16(w1), b1, gelu_aux=u, gelu=True, drop=drop1)
-            x2 = gemm.linear_fwd(h, store.bf16(w2), b2, resid=x1, drop=drop2)
+            x2 = gemm.linear_fwd(h, store.bf16(w2), b2, resid=x1, drop=drop2, drop_path=_dp(dpm, N))
         else:
             # fp8 forward GEMMs (e4m3 x e4m3, per-tensor delayed scaling); everything the backward
             # saves stays bf16, so the backward below is unchanged
@@ -280,6 +303,7 @@ class EncoderBlockFn(torch.autograd.Function):
         if need_bwd:
             ctx.save_for_backward(x, xn1, mean1, rstd1, qkv, o, lse, x1, xn2, mean2, rstd2, u, h)
         ctx.meta = (B, N, H, scale, store, drop1, drop2, dropa, params)
+        ctx.dpath = (dpa, dpm)
         if f8 is None:
             ctx.acts8 = None
         return x2
@@ -290,6 +314,7 @@ class EncoderBlockFn(torch.autograd.Function):
         _ext.deterministic()  # native flag follows torch.use_deterministic_algorithms from this kernel on
         x, xn1, mean1, rstd1, qkv, o, lse, x1, xn2, mean2, rstd2, u, h = ctx.saved_tensors
         B, N, H, scale, store, drop1, drop2, dropa, params = ctx.meta
+        dpa, dpm = ctx.dpath
         ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, w1, b1, w2, b2 = params
         aseed, aoff, ap = gemm._drop_args(dropa)
         g = store.grad_dest
@@ -357,9 +382,10 @@ class EncoderBlockFn(torch.autograd.Function):
             # last block: the column-sum pass that reduces d(b2) (and applies the fc2 dropout) also
             # writes dz2's e5m2 copy for the fp8 fc2 dgrad once that slot is calibrated
             prod = f8d[0].grad_producer(f8d[1], 0) if f8d is not None and store.bf16_t(w2) is not None else None
-            if drop2 is not None:
+            if drop2 is not None or dpm is not None:
+                # (drop path: dz2 = s_m * mask2 * dx2, the last block has no next block's LayerNorm backward to ride on)
                 dz2 = torch.empty_like(dx2)
-                r = gemm.bias_grad(dx2, g(b2), drop=drop2, dz=dz2, quant=prod)
+                r = gemm.bias_grad(dx2, g(b2), drop=drop2, dz=dz2, quant=prod, drop_path=_dp(dpm, N))
             else:
                 dz2 = dx2
                 r = gemm.bias_grad(dx2, g(b2), quant=prod) if (b2.requires_grad or prod is not None) else None
@@ -391,13 +417,17 @@ class EncoderBlockFn(torch.autograd.Function):
         # dx1 = dx2 + LN2'(dxn2); d(bo) = colsum(dx1) reduced in the same kernel; on the fp8 path the
         # kernel also writes dx1's e5m2 copy for the out-proj dgrad (grad slot 2) once it is calibrated
         q_kw, q_dx1 = _ln_grad_quant(f8d, 2, dx1.shape, dx1.device)
-        ext.layernorm_bwd(dxn2, D, x1, D, mean2, rstd2, ln2w, dx2, D, dx1, D, g(ln2w), g(ln2b), T, dsum=g(bo), **q_kw)
+        # drop path: the same pass also writes dz1 = s_a * dx1, the gradient of the attention branch
+        # (out-projection dgrad / weight gradient operand), and d(bo) becomes colsum(dz1)
+        dz1 = torch.empty_like(dx1) if dpa is not None else dx1
+        ext.layernorm_bwd(dxn2, D, x1, D, mean2, rstd2, ln2w, dx2, D, dx1, D, g(ln2w), g(ln2b), T, dsum=g(bo),
+                          **(dict(dz=dz1, **gemm._drop_path_kw(_dp(dpa, N))) if dpa is not None else {}), **q_kw)
         if q_dx1 is not None:
             pre_q[2] = q_dx1
         store.grad_ready([w2, b2, w1, b1, ln2w, ln2b])
-        # ---- attention branch: x1 = x + (attn(qkv(xn1)) . Wo^T + bo)
+        # ---- attention branch: x1 = x + s_a * (attn(qkv(xn1)) . Wo^T + bo)
         gwo, gwqkv = g(wo), g(wqkv)
-        do = dgrad(dx1, wo, 2)
+        do = dgrad(dz1, wo, 2)
         gbqkv = g(bqkv)
         side_db = False
         db_part = None
@@ -447,7 +477,7 @@ class EncoderBlockFn(torch.autograd.Function):
             elif side_db:
                 gemm.bias_grad(dqkv, gbqkv)
             if gwo is not None:
-                wgrad(dx1, o, gwo, 2, 1)
+                wgrad(dz1, o, gwo, 2, 1)
             if gwqkv is not None:
                 wgrad(dqkv, xn1, gwqkv, 3, 0)
 
@@ -464,13 +494,14 @@ class EncoderBlockFn(torch.autograd.Function):
                 side_db = False
             else:
                 pre_q[3] = f8d[0].grad_quant(dqkv, f8d[1], 3)
-        store.on_side(attn_wgrads, dx1, o, dqkv, xn1, do, *(() if db_part is None else (db_part,)), *side8(2, 3))
+        store.on_side(attn_wgrads, dz1, o, dqkv, xn1, do, *(() if db_part is None else (db_part,)), *side8(2, 3))
         dxn1 = dgrad(dqkv, wqkv, 3)
         dx = torch.empty_like(dx2)
         if prev is not None:
             # the previous block's fc2 dropout backward and bias gradient ride along with dx
             seed, soff, p = gemm._drop_args(prev.drop2)
-            dzp = torch.empty_like(dx2) if seed is not None else None
+            dp_kw = gemm._drop_path_kw(_dp(prev.dp2, N))  # its MLP-branch drop path: dz = s_m * mask2 * dx
+            dzp = torch.empty_like(dx2) if seed is not None or dp_kw else None
             # fp8: the previous block's dz2 (= dz, or dx without dropout) leaves as e5m2 too (its grad slot 0)
             pf8 = (f8d[0], f8d[1] - 1) if f8d is not None and f8d[1] > 0 else None
             q_kw, q_dz = _ln_grad_quant(pf8, 0, dx.shape, dx.device)
@@ -480,7 +511,7 @@ class EncoderBlockFn(torch.autograd.Function):
                           and prev.w2 is not None and store.bf16_t(prev.w2) is not None
                           and pf8[0].wgrad_ready(pf8[1], 0, 3))
             ext.layernorm_bwd(dxn1, D, x, D, mean1, rstd1, ln1w, dx1, D, dx, D, g(ln1w), g(ln1b), T,
-                              dsum=g(prev.b2), dz=dzp, seed=seed, seed_offset=soff, drop_p=p, dz_nostore=dz_nostore, **q_kw)
+                              dsum=g(prev.b2), dz=dzp, seed=seed, seed_offset=soff, drop_p=p, dz_nostore=dz_nostore, **dp_kw, **q_kw)
             if dzp is not None:
                 _poison(dzp, dz_nostore)
             prev.dz2, prev.dz2_q, prev.done = dzp, q_dz, True
@@ -510,13 +541,14 @@ class EncoderBlockClsFn(torch.autograd.Function):
     rows only, ``[B, D]``. LN1 and the qkv GEMM (and, backward, the qkv dgrad / weight gradient and the
     LN1 backward) run on every token, since every token's K and V feed the class-token query; the
     attention (csrc/attention.hip attn_cls_*), out-projection, LN2 and the MLP run on B rows. Dropout
-    masks are those of rows ``b * N`` of the full tensors, bit for bit (``drop_row_mul``). bf16 only,
-    no attention dropout (``cls_last_block_ok``)."""
+    masks are those of rows ``b * N`` of the full tensors, bit for bit (``drop_row_mul``); drop path draws
+    per sample, so the B-row tensors take it with one row per sample. bf16 only, no attention dropout
+    (``cls_last_block_ok``)."""
 
     @staticmethod
     def forward(ctx, x, B, N, H, eps1, eps2, store, drops, links, *params):
         ext = _ext.ext()
-        drop1, drop2, _ = drops
+        drop1, drop2, _, dpa, dpm = _split_drops(drops)
         ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, w1, b1, w2, b2 = params
         T, D = x.shape
         ctx.links = links if links is not None else (None, None)
@@ -527,14 +559,15 @@ class EncoderBlockClsFn(torch.autograd.Function):
         qkv = gemm.linear_fwd(xn1, store.bf16(wqkv), bqkv)
         o, lse = ext.attn_cls_fwd(qkv, B, N, H, scale)
         xc = x.view(B, N, D)[:, 0]  # the class-token rows, in place (row stride N * D)
-        x1 = gemm.linear_fwd(o, store.bf16(wo), bo, resid=xc)
+        x1 = gemm.linear_fwd(o, store.bf16(wo), bo, resid=xc, drop_path=_dp(dpa, 1))
         xn2, mean2, rstd2 = ext.layernorm_fwd(x1, ln2w, ln2b, eps2, B, D)
         u = torch.empty(B, M, dtype=torch.bfloat16, device=x.device) if need_bwd else None
         h = gemm.linear_fwd(xn2, store.bf16(w1), b1, gelu_aux=u, gelu=True, drop=drop1, drop_row_mul=N)
-        x2 = gemm.linear_fwd(h, store.bf16(w2), b2, resid=x1, drop=drop2, drop_row_mul=N)
+        x2 = gemm.linear_fwd(h, store.bf16(w2), b2, resid=x1, drop=drop2, drop_row_mul=N, drop_path=_dp(dpm, 1))
         if need_bwd:
             ctx.save_for_backward(x, xn1, mean1, rstd1, qkv, o, lse, x1, xn2, mean2, rstd2, u, h)
         ctx.meta = (B, N, H, scale, store, drop2, params)
+        ctx.dpath = (dpa, dpm)
         return x2
 
     @staticmethod
@@ -543,6 +576,7 @@ class EncoderBlockClsFn(torch.autograd.Function):
         det = _ext.deterministic()  # native flag follows torch.use_deterministic_algorithms from this kernel on
         x, xn1, mean1, rstd1, qkv, o, lse, x1, xn2, mean2, rstd2, u, h = ctx.saved_tensors
         B, N, H, scale, store, drop2, params = ctx.meta
+        dpa, dpm = ctx.dpath
         ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, w1, b1, w2, b2 = params
         g = store.grad_dest
         dx2 = dx2.contiguous()  # [B, D]: the gradient of the class-token rows
@@ -556,9 +590,9 @@ class EncoderBlockClsFn(torch.autograd.Function):
             return out
 
         # ---- MLP branch on B rows (see EncoderBlockFn.backward)
-        if drop2 is not None:
+        if drop2 is not None or dpm is not None:
             dz2 = torch.empty_like(dx2)
-            gemm.bias_grad(dx2, g(b2), drop=drop2, dz=dz2, row_mul=N)
+            gemm.bias_grad(dx2, g(b2), drop=drop2, dz=dz2, row_mul=N, drop_path=_dp(dpm, 1))
         else:
             dz2 = dx2
             if b2.requires_grad:
@@ -578,31 +612,34 @@ class EncoderBlockClsFn(torch.autograd.Function):
         store.on_side(mlp_wgrads, dz2, h, du, xn2)
         dxn2 = dgrad(du, w1, 1)
         dx1 = torch.empty_like(dx2)
-        ext.layernorm_bwd(dxn2, D, x1, D, mean2, rstd2, ln2w, dx2, D, dx1, D, g(ln2w), g(ln2b), B, dsum=g(bo))
+        dz1 = torch.empty_like(dx1) if dpa is not None else dx1  # drop path: s_a * dx1 (see EncoderBlockFn.backward)
+        ext.layernorm_bwd(dxn2, D, x1, D, mean2, rstd2, ln2w, dx2, D, dx1, D, g(ln2w), g(ln2b), B, dsum=g(bo),
+                          **(dict(dz=dz1, **gemm._drop_path_kw(_dp(dpa, 1))) if dpa is not None else {}))
         store.grad_ready([w2, b2, w1, b1, ln2w, ln2b])
         # ---- attention branch: the class-token query against every token's K and V
         gwo, gwqkv, gbqkv = g(wo), g(wqkv), g(bqkv)
-        do = dgrad(dx1, wo, 2)
+        do = dgrad(dz1, wo, 2)
         dqkv, dq0 = ext.attn_cls_bwd(do, qkv, o, lse, B, N, H, scale)
 
         def attn_wgrads():
             if gbqkv is not None:
                 ext.attn_cls_dbias(dq0, do, gbqkv.view(-1))
             if gwo is not None:
-                gemm.linear_wgrad(dx1, o, gwo)
+                gemm.linear_wgrad(dz1, o, gwo)
             if gwqkv is not None:
                 gemm.linear_wgrad(dqkv, xn1, gwqkv)
 
-        store.on_side(attn_wgrads, dx1, o, dqkv, xn1, do, dq0)
+        store.on_side(attn_wgrads, dz1, o, dqkv, xn1, do, dq0)
         dxn1 = dgrad(dqkv, wqkv, 3)
         dx = torch.empty_like(x)
         # dx = LN1'(dxn1) on every row + dx1 on the class-token rows (compact: no zero-filled carrier)
         if prev is not None:
             # the previous block's fc2 dropout backward and bias gradient ride along with dx
             seed, soff, p = gemm._drop_args(prev.drop2)
-            dzp = torch.empty_like(x) if seed is not None else None
+            dp_kw = gemm._drop_path_kw(_dp(prev.dp2, N))  # every token row of the previous block: N rows per sample
+            dzp = torch.empty_like(x) if seed is not None or dp_kw else None
             ext.layernorm_bwd(dxn1, D, x, D, mean1, rstd1, ln1w, dx1, D, dx, D, g(ln1w), g(ln1b), T,
-                              dsum=g(prev.b2), dz=dzp, seed=seed, seed_offset=soff, drop_p=p, dres_every=N)
+                              dsum=g(prev.b2), dz=dzp, seed=seed, seed_offset=soff, drop_p=p, dres_every=N, **dp_kw)
             prev.dz2, prev.dz2_q, prev.done = dzp, None, True
         else:
             ext.layernorm_bwd(dxn1, D, x, D, mean1, rstd1, ln1w, dx1, D, dx, D, g(ln1w), g(ln1b), T, dres_every=N)

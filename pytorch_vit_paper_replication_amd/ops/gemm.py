@@ -107,8 +107,13 @@ def _small_splitk(T: int, N: int, K: int) -> int:
 DGRAD_TAIL_UNITS = 64
 
 
-def _gemm(*args, tile: int, colsum=None, tail_limit: int = 0, drop_row_mul: int = 0):
-    _ext.ext().gemm(*args, tile, colsum=colsum, tail_limit=tail_limit, drop_row_mul=drop_row_mul)
+# a drop-path (stochastic depth) site: (seed tensor, site offset, rate, rows per sample); the sample of
+# row r is r // rows_per_sample (csrc/kernels.h DropSite)
+DropPath = Optional[Tuple[torch.Tensor, int, float, int]]
+
+
+def _gemm(*args, tile: int, colsum=None, tail_limit: int = 0, drop_row_mul: int = 0, drop_path: DropPath = None):
+    _ext.ext().gemm(*args, tile, colsum=colsum, tail_limit=tail_limit, drop_row_mul=drop_row_mul, **_drop_path_kw(drop_path))
 
 
 def _drop_args(drop: Drop):
@@ -117,13 +122,27 @@ def _drop_args(drop: Drop):
     return drop[0], int(drop[1]), float(drop[2])
 
 
+def _drop_path_kw(drop_path: DropPath) -> dict:
+    """The kernels' ``dp_*`` keyword arguments of a drop-path site ({}: none, today's call)."""
+    if drop_path is None or drop_path[2] <= 0.0:
+        return {}
+    seed, off, p, rows = drop_path
+    return dict(dp_seed=seed, dp_offset=int(off), dp_p=float(p), dp_rows=int(rows))
+
+
 def linear_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *,
                resid: Optional[torch.Tensor] = None, drop: Drop = None, gelu_aux: Optional[torch.Tensor] = None,
                gelu: bool = False,
                addend: Optional[torch.Tensor] = None, addend_period: int = 0,
                row_remap: Tuple[int, int, int] = (0, 0, 0), out: Optional[torch.Tensor] = None,
-               drop_row_mul: int = 0) -> torch.Tensor:
+               drop_row_mul: int = 0, drop_path: DropPath = None) -> torch.Tensor:
     """y = resid + dropout(x.w^T + bias + addend[row % period]).
+
+    ``drop_path`` = (seed, site offset, p, rows per sample) with p > 0: stochastic depth of the residual
+    branch, y = resid + s[row // rows_per_sample] * dropout(x.w^T + bias) with s = 0 or 1 / (1 - p) per
+    sample, drawn by the epilogue from the device counter (needs ``resid``; not with GELU / addend /
+    row_remap). The call is routed away from the paths without the term (split-K, the wave-specialised
+    tile). p = 0 is exactly the call without it.
 
     ``drop_row_mul`` = n > 1: the rows of ``x`` are a compact copy of every n-th row of a ``[T * n, K]``
     token matrix (its class-token rows); row m draws the dropout mask of row ``m * n`` of the full
@@ -138,13 +157,18 @@ def linear_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = 
         out = torch.empty(T, N, dtype=torch.bfloat16, device=x.device)
     seed, soff, p = _drop_args(drop)
     epi = EPI_GELU if (gelu or gelu_aux is not None) else EPI_BF16
+    if drop_path is not None and drop_path[2] <= 0.0:
+        drop_path = None
+    if drop_path is not None and (resid is None or epi != EPI_BF16 or addend is not None or row_remap[0]):
+        raise ValueError("drop_path needs the residual epilogue (resid given; no GELU, addend or row_remap)")
     if drop_row_mul > 1 and p > 0.0:
         if addend is not None or row_remap[0]:
             raise ValueError("drop_row_mul does not combine with addend / row_remap")
         _gemm(x, True, w, True, out, T, N, K, epi, bias, resid, None, 0, gelu_aux, 0, 0, 0, seed, soff, p, 0,
-              tile=0, drop_row_mul=int(drop_row_mul))
+              tile=0, drop_row_mul=int(drop_row_mul), drop_path=drop_path)
         return out
-    S = _small_splitk(T, N, K) if (p == 0.0 and gelu_aux is None and addend is None and row_remap[0] == 0) else 0
+    S = _small_splitk(T, N, K) if (p == 0.0 and gelu_aux is None and addend is None and row_remap[0] == 0
+                                   and drop_path is None) else 0
     if S:
         # serving-size batch: split K over workgroups (fp32 partials, tile 14), then one pass sums
         # them and applies bias / GELU / residual
@@ -156,9 +180,11 @@ def linear_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = 
         ext.splitk_epilogue(ws, nsplit, out, bias, resid, epi == EPI_GELU)
         return out
     kind = "gelu" if epi == EPI_GELU else "resid" if resid is not None else "bias"
+    tile = _tile(T, N, K, "fwd")
+    if addend is None and row_remap[0] == 0 and drop_path is None:  # (the wave-specialised kernel has no drop-path term)
+        tile = _ws_tile(kind, tile)
     _gemm(x, True, w, True, out, T, N, K, epi, bias, resid, addend, addend_period, gelu_aux,
-          row_remap[0], row_remap[1], row_remap[2], seed, soff, p, 0,
-          tile=_ws_tile(kind, _tile(T, N, K, "fwd")) if addend is None and row_remap[0] == 0 else _tile(T, N, K, "fwd"))
+          row_remap[0], row_remap[1], row_remap[2], seed, soff, p, 0, tile=tile, drop_path=drop_path)
     return out
 
 
@@ -292,8 +318,11 @@ def linear_wgrad(dy: torch.Tensor, x: torch.Tensor, out: torch.Tensor) -> torch.
 
 
 def bias_grad(dy: torch.Tensor, db: Optional[torch.Tensor], *, drop: Drop = None,
-              dz: Optional[torch.Tensor] = None, quant=None, row_mul: int = 1):
+              dz: Optional[torch.Tensor] = None, quant=None, row_mul: int = 1, drop_path: DropPath = None):
     """db += column sums of (mask * dy); writes the masked gradient to dz when given.
+
+    ``drop_path`` = (seed, site offset, p, rows per sample): the branch's stochastic-depth backward in the
+    same pass, dz = s[row // rows_per_sample] * mask * dy (independent of ``row_mul``; not with ``quant``).
 
     ``row_mul`` = n > 1: ``dy`` holds every n-th row of a ``[T * n, N]`` gradient (the class-token
     rows, compact); row m takes the mask of row ``m * n`` there.
@@ -304,8 +333,10 @@ def bias_grad(dy: torch.Tensor, db: Optional[torch.Tensor], *, drop: Drop = None
     T, N = dy.shape
     seed, soff, p = _drop_args(drop)
     if quant is None:
-        _ext.ext().colsum(dy, T, N, db, dz, seed, soff, p, row_mul=int(row_mul))
+        _ext.ext().colsum(dy, T, N, db, dz, seed, soff, p, row_mul=int(row_mul), **_drop_path_kw(drop_path))
         return None
+    if _drop_path_kw(drop_path):
+        raise ValueError("bias_grad: drop_path does not combine with the fp8 copy (quant)")
     meta, slot = quant
     q = torch.empty(T, N, dtype=torch.uint8, device=dy.device)
     _ext.ext().colsum(dy, T, N, db, dz, seed, soff, p, q_out=q, q_scale=meta.qscale[slot:slot + 1],

@@ -90,6 +90,10 @@ def save_checkpoint(target_dir: str, model: torch.nn.Module, optimizer=None, lr_
         # fused-path state outside state_dict(): the device dropout counter and the fp8 scaling
         # histories; without them a resumed run draws other dropout masks / re-calibrates fp8
         state["runtime"] = rt()
+    cfg = getattr(_unwrap(model), "config", None)
+    if isinstance(cfg, dict):
+        # the constructor arguments and the options set by method (``set_drop_path``): numbers and strings
+        state["config"] = dict(cfg)
     if model_ema is not None:
         # tensors and numbers only: load_checkpoint reads with weights_only=True
         state["model_ema"] = {"params": model_ema.state_dict(), "num_updates": int(model_ema.num_updates),
@@ -102,7 +106,11 @@ def save_checkpoint(target_dir: str, model: torch.nn.Module, optimizer=None, lr_
 
 def load_checkpoint(path: str, model: torch.nn.Module, optimizer=None, lr_scheduler=None, map_location="cpu",
                     restore_rng: bool = True, model_ema=None) -> Dict[str, Any]:
-    """Restores state saved by ``save_checkpoint``; returns ``{"epoch", "results"}``.
+    """Restores state saved by ``save_checkpoint``; returns ``{"epoch", "results", "config"}``.
+
+    ``config`` is the saved model's ``config`` dict (None for a model without one, or an older file). It is
+    returned, not applied: options that live there and not in ``state_dict()`` (``set_drop_path``) are the
+    caller's to set again, e.g. ``model.set_drop_path(cfg["drop_path"], cfg["drop_path_schedule"])``.
 
     The file is read with ``weights_only=True``: everything ``save_checkpoint`` writes (tensors,
     dicts/lists of numbers, the optimizer and LR-scheduler state dicts, RNG byte tensors) loads
@@ -138,4 +146,4 @@ def load_checkpoint(path: str, model: torch.nn.Module, optimizer=None, lr_schedu
                 torch.cuda.set_rng_state_all(state["cuda_rng"])
             except Exception:
                 pass
-    return {"epoch": state.get("epoch", 0), "results": state.get("results", {})}
+    return {"epoch": state.get("epoch", 0), "results": state.get("results", {}), "config": state.get("config")}
