@@ -56,6 +56,9 @@ def build_parser():
                    help="ViT: stochastic depth, the last block's drop rate (0: off; not with --dtype fp8)")
     p.add_argument("--drop-path-schedule", choices=["linear", "constant"], default="linear",
                    help="with --drop-path: rates rising linearly with depth from 0 to RATE, or RATE in every block")
+    p.add_argument("--patch-dropout", type=float, default=0.0, metavar="RATE",
+                   help="ViT: train on a random subset of each image's patch tokens, dropping this fraction "
+                        "(0: off; evaluation sees every patch; not with --dtype fp8)")
     p.add_argument("--deterministic", action="store_true",
                    help="fixed-order reductions instead of float atomics: bitwise-repeatable gradients")
     p.add_argument("--bucket-mb", type=float, default=28.0, help="DDP gradient bucket size (MiB)")
@@ -111,6 +114,12 @@ def main(argv=None) -> int:
         raise SystemExit("--drop-path applies to the ViT models")
     if args.drop_path and args.dtype == "fp8":
         raise SystemExit("--drop-path does not combine with --dtype fp8")
+    if args.patch_dropout and args.model == "tinyvgg":
+        raise SystemExit("--patch-dropout applies to the ViT models")
+    if args.patch_dropout and args.dtype == "fp8":
+        raise SystemExit("--patch-dropout does not combine with --dtype fp8")
+    if not 0.0 <= args.patch_dropout < 1.0:
+        raise SystemExit("--patch-dropout must be in [0, 1)")
     if args.model_ema_warmup and args.model_ema is None:
         raise SystemExit("--model-ema-warmup needs --model-ema")
     if not args.device_preprocess and (args.augment != "none" or args.source_size is not None):
@@ -133,7 +142,7 @@ def main(argv=None) -> int:
     else:
         drop = {} if args.dropout is None else dict(mlp_dropout=args.dropout, embedding_dropout=args.dropout)
         model = vit(args.model, image_size=args.image_size, num_classes=ncls, drop_path=args.drop_path,
-                    drop_path_schedule=args.drop_path_schedule, **drop)
+                    drop_path_schedule=args.drop_path_schedule, patch_dropout=args.patch_dropout, **drop)
         if args.dtype == "fp8":  # before a resume: the checkpoint's fp8 scaling state needs it
             model.enable_fp8(wgrad=not args.fp8_bf16_wgrad, grad_fmt=args.fp8_grad)
         if args.device_preprocess:
@@ -163,6 +172,9 @@ def main(argv=None) -> int:
             now = (cfg.get("drop_path", 0.0), cfg.get("drop_path_schedule", "linear"))
             if was != now and (was[0] or now[0]):
                 print(f"[INFO] The run continues with --drop-path {now[0]} ({now[1]}); the checkpoint was written with {was[0]} ({was[1]})")
+            was, now = saved.get("patch_dropout", 0.0), cfg.get("patch_dropout", 0.0)
+            if was != now:
+                print(f"[INFO] The run continues with --patch-dropout {now}; the checkpoint was written with {was}")
     net = (DistributedDataParallel(model, bucket_cap_mb=args.bucket_mb,
                                    comm_dtype=torch.bfloat16 if args.comm_dtype == "bf16" else None)
            if is_dist() else model)

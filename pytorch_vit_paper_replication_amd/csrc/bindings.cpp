@@ -493,12 +493,62 @@ const pvr::MixRow* mix_rows(const c10::optional<torch::Tensor>& mix, const c10::
   return reinterpret_cast<const pvr::MixRow*>(mix->data_ptr());
 }
 
+// Patch dropout's keep table (csrc/elementwise.hip patch_keep_kernel): (keep int32 [B, n_keep], inv int32
+// [B, n_p]) of the site `site_offset` at the counter value *seed. The fused forward's draw, and the
+// tests' and the reference path's replay of it.
+std::tuple<torch::Tensor, torch::Tensor> patch_keep_table(torch::Tensor seed, int64_t site_offset, int64_t B, int64_t n_p,
+                                                          int64_t n_keep) {
+  TORCH_CHECK(seed.is_cuda() && seed.scalar_type() == torch::kInt64 && seed.numel() >= 1,
+              "patch_keep_table: seed must be an int64 tensor on the GPU");
+  TORCH_CHECK(n_p >= 1 && n_p <= 4096, "patch_keep_table: n_p must be in [1, 4096], got ", n_p);
+  TORCH_CHECK(n_keep >= 1 && n_keep <= n_p, "patch_keep_table: n_keep must be in [1, n_p = ", n_p, "], got ", n_keep);
+  TORCH_CHECK(B >= 0 && B * n_p < (int64_t(1) << 32), "patch_keep_table: B * n_p must be below 2^32");
+  auto keep = torch::empty({B, n_keep}, seed.options().dtype(torch::kInt32));
+  auto inv = torch::empty({B, n_p}, seed.options().dtype(torch::kInt32));
+  check(pvr_patch_keep(reinterpret_cast<const uint64_t*>(seed.data_ptr()), (uint64_t)site_offset, (int)B, (int)n_p, (int)n_keep,
+                       keep.data_ptr<int>(), inv.data_ptr<int>(), stream()),
+        "patch_keep_table");
+  return std::make_tuple(keep, inv);
+}
+
+// A keep table as a kernel argument: contiguous int32 [B, n_keep] on `like`'s device, 1 <= n_keep <= n_p
+const int* keep_rows(const c10::optional<torch::Tensor>& keep, int64_t B, int64_t n_p, const torch::Tensor& like, int64_t* n_keep,
+                     const char* what) {
+  *n_keep = 0;
+  if (!keep.has_value() || !keep->defined()) return nullptr;
+  TORCH_CHECK(keep->is_cuda() && keep->device() == like.device() && keep->scalar_type() == torch::kInt32 && keep->dim() == 2 &&
+                  keep->is_contiguous() && keep->size(0) == B && keep->size(1) >= 1 && keep->size(1) <= n_p,
+              what, ": keep must be contiguous int32 [", B, ", 1 .. ", n_p, "] on the input's device");
+  *n_keep = keep->size(1);
+  return keep->data_ptr<int>();
+}
+
+// the embedding GEMM's position addend under patch dropout (csrc/elementwise.hip pos_gather_kernel)
+torch::Tensor pos_gather(torch::Tensor pos, torch::Tensor keep) {
+  TORCH_CHECK(pos.dim() == 2 && pos.is_contiguous() && pos.size(0) >= 2 && pos.size(1) % 4 == 0, "pos_gather: pos must be contiguous [n_p + 1, D], D % 4 == 0");
+  const int64_t n_p = pos.size(0) - 1, D = pos.size(1);
+  TORCH_CHECK(keep.dim() == 2, "pos_gather: keep must be [B, n_keep]");
+  const int64_t B = keep.size(0);
+  int64_t n_keep = 0;
+  const int* kp = keep_rows(keep, B, n_p, pos, &n_keep, "pos_gather");
+  TORCH_CHECK(B * (n_keep + 1) < (int64_t(1) << 31), "pos_gather: too many rows");
+  auto out = torch::empty({B * (n_keep + 1), D}, pos.options());
+  check(pvr_pos_gather(f32(pos, "pos"), kp, out.data_ptr<float>(), (int)B, (int)n_p, (int)n_keep, (int)D, stream()), "pos_gather");
+  return out;
+}
+
 void im2col(torch::Tensor img, torch::Tensor out, int64_t P, int64_t Kp, c10::optional<torch::Tensor> mix,
-            c10::optional<torch::Tensor> mix_host) {
+            c10::optional<torch::Tensor> mix_host, c10::optional<torch::Tensor> keep) {
   TORCH_CHECK(img.is_contiguous() && img.dim() == 4, "im2col: img must be contiguous NCHW");
   const pvr::MixRow* mp = mix_rows(mix, mix_host, img.size(0), img.size(2), img.size(3), img, "im2col");
-  if (mp) {  // the plain call keeps its checks; a plan adds those that keep the second read in bounds
-    const int64_t rows = P > 0 ? img.size(0) * (img.size(2) / P) * (img.size(3) / P) : -1;
+  int64_t n_keep = 0;
+  const int* kp = nullptr;
+  if (keep.has_value() && keep->defined()) {  // (the plain call keeps its checks, as with a plan below)
+    TORCH_CHECK(P > 0, "im2col: patch size");
+    kp = keep_rows(keep, img.size(0), (img.size(2) / P) * (img.size(3) / P), img, &n_keep, "im2col");
+  }
+  if (mp || kp) {  // the plain call keeps its checks; a plan adds those that keep the second read in bounds
+    const int64_t rows = P > 0 ? img.size(0) * (kp ? n_keep : (img.size(2) / P) * (img.size(3) / P)) : -1;
     TORCH_CHECK(img.is_cuda() && P > 0 && img.size(2) % P == 0 && img.size(3) % P == 0 && Kp % 8 == 0 &&
                     Kp >= img.size(1) * P * P,
                 "im2col: the image must be a GPU tensor whose sides are multiples of the patch size, Kp a multiple of 8 >= C*P*P");
@@ -507,7 +557,7 @@ void im2col(torch::Tensor img, torch::Tensor out, int64_t P, int64_t Kp, c10::op
                 "im2col: out must be contiguous bf16 [", rows, ", ", Kp, "] on the image's device");
   }
   check(pvr_im2col(f32(img, "img"), bf_mut(out, "out"), (int)img.size(0), (int)img.size(1), (int)img.size(2), (int)img.size(3),
-                   (int)P, (int)Kp, mp, stream()),
+                   (int)P, (int)Kp, mp, kp, (int)n_keep, stream()),
         "im2col");
 }
 
@@ -517,7 +567,7 @@ void im2col(torch::Tensor img, torch::Tensor out, int64_t P, int64_t Kp, c10::op
 // the 8-byte-load path ran, 0 for the per-element path (decided here from data_ptr and strides).
 int64_t im2col_u8(torch::Tensor img, torch::Tensor out, std::vector<double> mean, std::vector<double> stdv,
                   c10::optional<torch::Tensor> geom, int64_t H, int64_t W, int64_t P, int64_t Kp, c10::optional<torch::Tensor> mix,
-                  c10::optional<torch::Tensor> mix_host) {
+                  c10::optional<torch::Tensor> mix_host, c10::optional<torch::Tensor> keep) {
   TORCH_CHECK(img.is_cuda() && img.scalar_type() == torch::kUInt8, "im2col_u8: img must be a uint8 GPU tensor, got ",
               img.scalar_type(), " on ", img.device());
   TORCH_CHECK(img.dim() == 4, "im2col_u8: img must be [B, C, Hs, Ws], got ", img.dim(), " dims");
@@ -528,7 +578,9 @@ int64_t im2col_u8(torch::Tensor img, torch::Tensor out, std::vector<double> mean
   TORCH_CHECK(P > 0 && H > 0 && W > 0 && H % P == 0 && W % P == 0, "im2col_u8: output ", H, "x", W,
               " must be a positive multiple of the patch size ", P);
   TORCH_CHECK(Hs >= 1 && Ws >= 1 && Hs < (1 << 24) && Ws < (1 << 24), "im2col_u8: bad source size ", Hs, "x", Ws);
-  const int64_t rows = B * (H / P) * (W / P);
+  int64_t n_keep = 0;
+  const int* kp = keep_rows(keep, B, (H / P) * (W / P), img, &n_keep, "im2col_u8");
+  const int64_t rows = B * (kp ? n_keep : (H / P) * (W / P));
   TORCH_CHECK(Kp % 8 == 0 && Kp >= C * P * P, "im2col_u8: Kp must be a multiple of 8 and >= C*P*P");
   TORCH_CHECK(B < (1ll << 31) && rows < (1ll << 31) && Kp < (1ll << 31), "im2col_u8: sizes exceed 32 bits");
   TORCH_CHECK(out.is_cuda() && out.device() == img.device() && out.is_contiguous() && out.dim() == 2 && out.size(0) == rows &&
@@ -556,7 +608,7 @@ int64_t im2col_u8(torch::Tensor img, torch::Tensor out, std::vector<double> mean
     sd[c] = (float)stdv[c];
   }
   check(pvr_im2col_u8(ip, sb, sc, sy, sx, m, sd, gp, bf_mut(out, "out"), (int)B, (int)C, (int)Hs, (int)Ws, (int)H, (int)W, (int)P,
-                      (int)Kp, vec, mp, stream()),
+                      (int)Kp, vec, mp, kp, (int)n_keep, stream()),
         "im2col_u8");
   return vec;
 }
@@ -598,12 +650,28 @@ void cls_rows(torch::Tensor cls, torch::Tensor pos, torch::Tensor out, int64_t B
 
 void patch_bwd(torch::Tensor dE, int64_t B, int64_t ntok, int64_t D, c10::optional<torch::Tensor> dpos, c10::optional<torch::Tensor> dcls,
                c10::optional<torch::Tensor> dconv, c10::optional<torch::Tensor> dbias, c10::optional<torch::Tensor> seed,
-               int64_t seed_offset, double drop_p) {
+               int64_t seed_offset, double drop_p, c10::optional<torch::Tensor> inv, int64_t n_keep) {
   const pvr::DropSite d = drop_args(seed, seed_offset, drop_p, "patch_bwd");
-  TORCH_CHECK(dE.numel() == B * ntok * D, "patch_bwd: dE must hold B * ntok * D elements");
+  const int* ip = nullptr;
+  if (inv.has_value() && inv->defined()) {
+    // patch dropout: dE / dconv are the compact tensors of n_keep patches per sample, inv the slot table
+    TORCH_CHECK(B >= 1 && ntok >= 2 && D >= 8 && D % 8 == 0 && B * ntok < (int64_t(1) << 31), "patch_bwd: sizes");
+    TORCH_CHECK(inv->is_cuda() && inv->device() == dE.device() && inv->scalar_type() == torch::kInt32 && inv->is_contiguous() &&
+                    inv->dim() == 2 && inv->size(0) == B && inv->size(1) == ntok - 1,
+                "patch_bwd: inv must be contiguous int32 [", B, ", ", ntok - 1, "] on dE's device");
+    TORCH_CHECK(n_keep >= 1 && n_keep <= ntok - 1, "patch_bwd: n_keep must be in [1, ", ntok - 1, "], got ", n_keep);
+    TORCH_CHECK(dE.is_contiguous() && dE.numel() == B * (n_keep + 1) * D, "patch_bwd: dE must be contiguous and hold B * (n_keep + 1) * D elements");
+    if (dconv.has_value() && dconv->defined())
+      TORCH_CHECK(dconv->is_cuda() && dconv->scalar_type() == torch::kBFloat16 && dconv->is_contiguous() && dconv->numel() == B * n_keep * D,
+                  "patch_bwd: dconv must be contiguous bf16 and hold B * n_keep * D elements");
+    if (dpos.has_value() && dpos->defined()) TORCH_CHECK(dpos->numel() >= ntok * D, "patch_bwd: dpos must hold ntok * D elements");
+    ip = inv->data_ptr<int>();
+  } else {
+    TORCH_CHECK(dE.numel() == B * ntok * D, "patch_bwd: dE must hold B * ntok * D elements");
+  }
   auto ws = torch::empty({pvr_patch_bwd_ws_floats((int)B, (int)ntok, (int)D)}, dE.options().dtype(torch::kFloat32));
   check(pvr_patch_bwd(bf(dE, "dE"), (int)B, (int)ntok, (int)D, ws.data_ptr<float>(), opt_ptr<float>(dpos), opt_ptr<float>(dcls), opt_ptr<uint16_t>(dconv),
-                      opt_ptr<float>(dbias), d, stream()),
+                      opt_ptr<float>(dbias), d, ip, (int)n_keep, stream()),
         "patch_bwd");
 }
 
@@ -1250,11 +1318,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q_amax") = py::none(), py::arg("q_fmt") = 1, py::arg("row_mul") = 1, py::arg("dp_seed") = py::none(),
         py::arg("dp_offset") = 0, py::arg("dp_p") = 0.0, py::arg("dp_rows") = 1);
   m.def("im2col", &im2col, py::arg("img"), py::arg("out"), py::arg("P"), py::arg("Kp"), py::arg("mix") = py::none(),
-        py::arg("mix_host") = py::none());
+        py::arg("mix_host") = py::none(), py::arg("keep") = py::none());
   m.def("im2col_u8", &im2col_u8, py::arg("img"), py::arg("out"), py::arg("mean"), py::arg("std"), py::arg("geom"), py::arg("H"),
-        py::arg("W"), py::arg("P"), py::arg("Kp"), py::arg("mix") = py::none(), py::arg("mix_host") = py::none());
+        py::arg("W"), py::arg("P"), py::arg("Kp"), py::arg("mix") = py::none(), py::arg("mix_host") = py::none(),
+        py::arg("keep") = py::none());
+  m.def("patch_keep_table", &patch_keep_table, py::arg("seed"), py::arg("site_offset"), py::arg("B"), py::arg("n_p"), py::arg("n_keep"));
+  m.def("pos_gather", &pos_gather, py::arg("pos"), py::arg("keep"));
   m.def("cls_rows", &cls_rows);
-  m.def("patch_bwd", &patch_bwd);
+  m.def("patch_bwd", &patch_bwd, py::arg("dE"), py::arg("B"), py::arg("ntok"), py::arg("D"), py::arg("dpos"), py::arg("dcls"),
+        py::arg("dconv"), py::arg("dbias"), py::arg("seed"), py::arg("seed_offset"), py::arg("drop_p"), py::arg("inv") = py::none(),
+        py::arg("n_keep") = 0);
   m.def("xent", &xent, py::arg("logits"), py::arg("labels"), py::arg("dlogits"), py::arg("correct"), py::arg("grad_scale"),
         py::arg("mean") = py::none());
   m.def("xent_soft", &xent_soft, py::arg("logits"), py::arg("ya"), py::arg("yb"), py::arg("lam"), py::arg("eps"),

@@ -2,7 +2,9 @@
 //   * flat fp32 -> bf16 shadow cast of the parameter store
 //   * bias-gradient column sums, optionally fused with the dropout-mask backward
 //   * patch embedding: im2col gather (fp32 image -> bf16 patch rows), CLS rows, and the backward
-//     reduction of the embedding-dropout / position-embedding / CLS gradients.
+//     reduction of the embedding-dropout / position-embedding / CLS gradients;
+//   * patch dropout: the per-sample keep table (ranks of counter-hash keys), the gathered position
+//     addend, and the KEEP instantiations of the patchify kernels and of the backward's first pass.
 #include "common.h"
 #include "kernels.h"
 
@@ -148,6 +150,70 @@ __global__ void __launch_bounds__(256) drop_path_scale_kernel(const uint64_t* se
   if (b < B) out[b] = rng_keep(*seed_ptr + off, (uint64_t)b, thr) ? scale : 0.f;
 }
 
+// Patch dropout: which n_keep of a sample's np patches a training step keeps. The key of patch j of
+// sample b is the full 32-bit rng_hash(*seed_ptr + off, b * np + j) (B * np < 2^32, host-checked: the
+// index's high word is 0); the sample keeps the n_keep smallest (key, j) pairs, in ascending patch order:
+//   keep[b][s] = index of the s-th kept patch (strictly ascending), inv[b][j] = slot s of patch j or -1.
+// One workgroup per sample, keys in LDS (np <= PK_MAX). The rank of a patch is the number of smaller
+// pairs (np reads per patch, np^2 / 256 per thread: microseconds at np = 196 or 576); the ranks are a
+// permutation of 0 .. np - 1, so exactly n_keep patches have rank < n_keep. Their flags go to LDS as
+// one ballot word pair per wave and trip, and the compact slot is the popcount of the flags below j.
+constexpr int PK_MAX = 4096;
+__global__ void __launch_bounds__(256) patch_keep_kernel(const uint64_t* seed_ptr, uint64_t off, int np, int n_keep,
+                                                          int* __restrict__ keep, int* __restrict__ inv) {
+  __shared__ uint32_t keys[PK_MAX];
+  __shared__ uint32_t flags[PK_MAX / 32];
+  const int b = blockIdx.x;
+  const uint32_t key = rng_key(*seed_ptr + off);
+  for (int j = threadIdx.x; j < np; j += 256) keys[j] = rng_mix32(((uint32_t)b * (uint32_t)np + (uint32_t)j) ^ key);
+  __syncthreads();
+  const int trips = (np + 255) / 256;  // uniform: every lane takes part in every ballot
+  for (int t = 0; t < trips; ++t) {
+    const int j = t * 256 + threadIdx.x;
+    bool kept = false;
+    if (j < np) {
+      const uint32_t kj = keys[j];
+      int rank = 0;
+      for (int i = 0; i < np; ++i) {
+        const uint32_t ki = keys[i];
+        rank += (ki < kj || (ki == kj && i < j)) ? 1 : 0;
+      }
+      kept = rank < n_keep;
+    }
+    const uint64_t m = __builtin_amdgcn_ballot_w64(kept);
+    if ((threadIdx.x & 63) == 0) {  // patches j .. j + 63 (flags past np are 0)
+      flags[j >> 5] = (uint32_t)m;
+      flags[(j >> 5) + 1] = (uint32_t)(m >> 32);
+    }
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < np; j += 256) {
+    const uint32_t fw = flags[j >> 5];
+    int slot = __builtin_popcount(fw & ((1u << (j & 31)) - 1u));
+    for (int w = 0; w < (j >> 5); ++w) slot += __builtin_popcount(flags[w]);
+    const bool kept = (fw >> (j & 31)) & 1u;
+    inv[(int64_t)b * np + j] = kept ? slot : -1;
+    if (kept && slot < n_keep) keep[(int64_t)b * n_keep + slot] = j;
+  }
+}
+
+// The embedding GEMM's position addend under patch dropout: out [B][n_keep + 1][D] fp32 with row
+// 1 + s of sample b = pos[keep[b][s] + 1] (pos [np + 1][D]; row 0 = pos[0], which the GEMM does not read:
+// cls_rows_kernel adds it). One thread per float4.
+__global__ void __launch_bounds__(256) pos_gather_kernel(const float* __restrict__ pos, const int* __restrict__ keep,
+                                                          float* __restrict__ out, int B, int np, int n_keep, int D) {
+  const int d4 = D / 4;
+  const int64_t total = (int64_t)B * (n_keep + 1) * d4;
+  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int c = (int)(i % d4);
+    const int64_t r = i / d4;
+    const int n = (int)(r % (n_keep + 1));
+    const int64_t b = r / (n_keep + 1);
+    const int src = n == 0 ? 0 : min(max(keep[b * n_keep + n - 1], 0), np - 1) + 1;
+    ((float4*)out)[i] = ((const float4*)pos)[(int64_t)src * d4 + c];
+  }
+}
+
 // One mixed pixel of the patchify kernels' MIX variants (MixRow in kernels.h): fp32, contraction off
 PVR_DEV float mix_value(float own, float par, bool inside, float lam, float oml) {
 #pragma clang fp contract(off)
@@ -172,19 +238,23 @@ PVR_DEV MixRow mix_row(const MixRow* __restrict__ mix, int b, int B) {
 // MIX: sample b's pixels are blended with / replaced by those of sample mix[b].partner while they
 // are gathered (mixup / CutMix, see MixRow in kernels.h). A pixel whose weight is 0 or 1 is read from
 // one sample only, so CutMix moves the bytes of the plain gather; mixup reads the input twice.
-template <bool MIX>
+// KEEP (patch dropout, both patchify kernels): only n_keep patches per sample are gathered. Output row r
+// belongs to sample r / n_keep and holds patch keep[r] of it (keep [B][n_keep] int32, ascending per
+// sample: patch_keep_kernel); the pixels, the padding and the mix plan (a box is in image pixels) are
+// those of that patch in the plain kernel.
+template <bool MIX, bool KEEP = false>
 __global__ void __launch_bounds__(256) im2col_kernel(const float* __restrict__ img, uint16_t* __restrict__ out,
                                                       int B, int C, int H, int W, int P, int Kp,
-                                                      const MixRow* __restrict__ mix) {
+                                                      const MixRow* __restrict__ mix, const int* __restrict__ keep, int n_keep) {
   const int gw = W / P, np = (H / P) * gw;
   const int kc = C * P * P, k8 = Kp / 8;
   const bool vec = (P % 8 == 0) && (W % 4 == 0);
-  const int64_t total = (int64_t)B * np * k8;
+  const int64_t total = (int64_t)B * (KEEP ? n_keep : np) * k8;
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int k0 = (int)(i % k8) * 8;
     const int64_t rowi = i / k8;
-    const int pidx = (int)(rowi % np);
-    const int b = (int)(rowi / np);
+    const int pidx = KEEP ? min(max(keep[rowi], 0), np - 1) : (int)(rowi % np);
+    const int b = (int)(rowi / (KEEP ? n_keep : np));
     const int y0 = (pidx / gw) * P, x0 = (pidx % gw) * P;
     float v[8];
     if constexpr (MIX) {
@@ -309,11 +379,13 @@ PVR_DEV float u8_sample(const uint8_t* src_c, int64_t sy, int64_t sx, const floa
 
 // MIX (see im2col_kernel): the blend runs on the normalised fp32 values, each sample under its own
 // crop box, so the no-GEOM table then holds fp32 values instead of their bf16 roundings.
-template <bool GEOM, bool MIX>
+// KEEP: as in im2col_kernel.
+template <bool GEOM, bool MIX, bool KEEP = false>
 __global__ void __launch_bounds__(256) im2col_u8_kernel(const uint8_t* __restrict__ img, int64_t sb, int64_t sc, int64_t sy,
                                                          int64_t sx, U8Norm nrm, const float* __restrict__ geom,
                                                          uint16_t* __restrict__ out, int B, int C, int Hs, int Ws, int H, int W,
-                                                         int P, int Kp, int vec, const MixRow* __restrict__ mix) {
+                                                         int P, int Kp, int vec, const MixRow* __restrict__ mix,
+                                                         const int* __restrict__ keep, int n_keep) {
 #pragma clang fp contract(off)
   // Without GEOM a pixel is one of 256 byte values: each block tabulates the normalised bf16 of every
   // (channel, byte) pair once, with the same operations and hence the same bits, and its loop does
@@ -330,12 +402,12 @@ __global__ void __launch_bounds__(256) im2col_u8_kernel(const uint8_t* __restric
   }
   const int gw = W / P, np = (H / P) * gw;
   const int kc = C * P * P, k8 = Kp / 8;
-  const int64_t total = (int64_t)B * np * k8;
+  const int64_t total = (int64_t)B * (KEEP ? n_keep : np) * k8;
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int k0 = (int)(i % k8) * 8;
     const int64_t rowi = i / k8;
-    const int pidx = (int)(rowi % np);
-    const int b = (int)(rowi / np);
+    const int pidx = KEEP ? min(max(keep[rowi], 0), np - 1) : (int)(rowi % np);
+    const int b = (int)(rowi / (KEEP ? n_keep : np));
     const int py = (pidx / gw) * P, px = (pidx % gw) * P;
     const uint8_t* src_b = img + b * sb;
     uint32_t h[8];  // bf16 bits
@@ -482,27 +554,56 @@ __global__ void __launch_bounds__(256) cls_rows_kernel(const float* __restrict__
 //  pass 2: thread = (8-column chunk, token) sums the groups, owns dpos[n] (and dcls for n = 0), and
 //          the block reduces its tokens' dbias partials in LDS into one partial row per token block;
 //  pass 3: the conv-bias gradient sums those rows in block order (deterministic, no atomics).
+// KEEP (patch dropout): dE is the compact [B][n_keep + 1][D] token gradient and inv [B][ntok - 1] gives the
+// compact slot of each patch (-1: dropped, patch_keep_kernel). The thread still owns position n of the
+// full sequence: for image b it reads compact row 1 + inv[b][n - 1] (row 0 for n = 0), masks it at that
+// compact element index (the forward's) and stores it to dconv [B * n_keep][D]; a dropped patch is
+// skipped, so a position no image of the group kept sums to exact zeros. ws / passes 2 and 3 are unchanged.
 constexpr int PB_BAT = 32, PB_UNROLL = 8;
+template <bool KEEP>
 __global__ void __launch_bounds__(256) patch_bwd_kernel(const uint16_t* __restrict__ dE, int B, int ntok, int D,
                                                          float* __restrict__ ws, uint16_t* __restrict__ dconv,
-                                                         const uint64_t* seed_ptr, uint64_t seed_off, uint32_t thr, float scale) {
+                                                         const uint64_t* seed_ptr, uint64_t seed_off, uint32_t thr, float scale,
+                                                         const int* __restrict__ inv, int n_keep) {
   const uint64_t seed = thr ? (*seed_ptr + seed_off) : 0ull;
   const int nch = D >> 3;
   const int flat = blockIdx.x * 256 + threadIdx.x;
   if (flat >= ntok * nch) return;
   const int n = flat / nch, c = flat - n * nch;
   const int b0 = blockIdx.y * PB_BAT, b1 = min(B, b0 + PB_BAT);
-  const int64_t img_stride = (int64_t)ntok * D;  // elements between consecutive images
-  const uint16_t* src = dE + (int64_t)n * D + c * 8;
+  const int rows_img = KEEP ? n_keep + 1 : ntok;          // token rows of one image in dE
+  const int64_t img_stride = (int64_t)rows_img * D;       // elements between consecutive images
+  const uint16_t* src = dE + (KEEP ? 0 : (int64_t)n * D) + c * 8;
   float s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   for (int bb = b0; bb < b1; bb += PB_UNROLL) {
     uint4 q[PB_UNROLL];
+    int row[PB_UNROLL];  // KEEP: the compact row of position n in image bb + u, -1: dropped
+    if constexpr (KEEP) {
 #pragma unroll
-    for (int u = 0; u < PB_UNROLL; ++u) q[u] = *(const uint4*)(src + (int64_t)min(bb + u, b1 - 1) * img_stride);
+      for (int u = 0; u < PB_UNROLL; ++u) {
+        row[u] = 0;
+        if (n > 0) {
+          const int sl = inv[(int64_t)min(bb + u, b1 - 1) * (ntok - 1) + n - 1];
+          row[u] = (sl >= 0 && sl < n_keep) ? sl + 1 : -1;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < PB_UNROLL; ++u) {
+        q[u] = make_uint4(0u, 0u, 0u, 0u);
+        if (row[u] >= 0) q[u] = *(const uint4*)(src + (int64_t)min(bb + u, b1 - 1) * img_stride + (int64_t)row[u] * D);
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < PB_UNROLL; ++u) q[u] = *(const uint4*)(src + (int64_t)min(bb + u, b1 - 1) * img_stride);
+    }
 #pragma unroll
     for (int u = 0; u < PB_UNROLL; ++u) {
       const int b = bb + u;
       if (b >= b1) break;
+      if constexpr (KEEP) {
+        if (row[u] < 0) continue;
+      }
+      const int tok = KEEP ? row[u] : n;  // the row's token index inside its image
       const uint32_t w[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
       float v[8];
 #pragma unroll
@@ -511,7 +612,7 @@ __global__ void __launch_bounds__(256) patch_bwd_kernel(const uint16_t* __restri
         v[2 * j + 1] = bf2f(w[j] >> 16);
       }
       if (thr) {
-        const uint64_t e0 = ((uint64_t)b * ntok + n) * D + c * 8;
+        const uint64_t e0 = ((uint64_t)b * rows_img + tok) * D + c * 8;
 #pragma unroll
         for (int j = 0; j < 8; j += 2) {
           bool k0, k1;
@@ -525,7 +626,7 @@ __global__ void __launch_bounds__(256) patch_bwd_kernel(const uint16_t* __restri
       if (n > 0 && dconv) {
         uint4 o;
         o.x = pack2bf(v[0], v[1]); o.y = pack2bf(v[2], v[3]); o.z = pack2bf(v[4], v[5]); o.w = pack2bf(v[6], v[7]);
-        *(uint4*)(dconv + ((int64_t)b * (ntok - 1) + n - 1) * D + c * 8) = o;
+        *(uint4*)(dconv + ((int64_t)b * (rows_img - 1) + tok - 1) * D + c * 8) = o;
       }
     }
   }
@@ -799,29 +900,57 @@ extern "C" hipError_t pvr_drop_path_scale(pvr::DropSite dpath, float* s_out, int
   return hipGetLastError();
 }
 
+extern "C" hipError_t pvr_patch_keep(const uint64_t* seed, uint64_t offset, int B, int np, int n_keep, int* keep, int* inv,
+                                     hipStream_t s) {
+  using namespace pvr;
+  if (!seed || !keep || !inv || np < 1 || np > PK_MAX || n_keep < 1 || n_keep > np || B < 0 || (int64_t)B * np >= (1ll << 32))
+    return hipErrorInvalidValue;
+  if (B == 0) return hipSuccess;
+  hipLaunchKernelGGL(patch_keep_kernel, dim3(B), dim3(256), 0, s, seed, offset, np, n_keep, keep, inv);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t pvr_pos_gather(const float* pos, const int* keep, float* out, int B, int np, int n_keep, int D, hipStream_t s) {
+  using namespace pvr;
+  if (!pos || !keep || !out || np < 1 || n_keep < 1 || n_keep > np || D < 4 || D % 4 || reinterpret_cast<uintptr_t>(pos) % 16 ||
+      reinterpret_cast<uintptr_t>(out) % 16)
+    return hipErrorInvalidValue;
+  const int64_t total = (int64_t)B * (n_keep + 1) * (D / 4);
+  if (total <= 0) return hipSuccess;
+  int64_t blocks = (total + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(pos_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, s, pos, keep, out, B, np, n_keep, D);
+  return hipGetLastError();
+}
+
 extern "C" hipError_t pvr_im2col(const float* img, uint16_t* out, int B, int C, int H, int W, int P, int Kp,
-                                 const pvr::MixRow* mix, hipStream_t s) {
+                                 const pvr::MixRow* mix, const int* keep, int n_keep, hipStream_t s) {
   using namespace pvr;
   if (Kp % 8 || (mix && reinterpret_cast<uintptr_t>(mix) % 16)) return hipErrorInvalidValue;
-  const int64_t total = (int64_t)B * (H / P) * (W / P) * (Kp / 8);
+  const int np = (H / P) * (W / P);
+  if (keep && (n_keep < 1 || n_keep > np)) return hipErrorInvalidValue;
+  const int64_t total = (int64_t)B * (keep ? n_keep : np) * (Kp / 8);
   if (total <= 0) return hipSuccess;
   int64_t blocks = (total + 255) / 256;
   if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(mix ? im2col_kernel<true> : im2col_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, img, out, B, C, H, W,
-                     P, Kp, mix);
+  const auto kern = keep ? (mix ? im2col_kernel<true, true> : im2col_kernel<false, true>)
+                         : (mix ? im2col_kernel<true> : im2col_kernel<false>);
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, s, img, out, B, C, H, W, P, Kp, mix, keep, keep ? n_keep : 0);
   return hipGetLastError();
 }
 
 extern "C" hipError_t pvr_im2col_u8(const uint8_t* img, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float* mean,
                                     const float* stdv, const float* geom, uint16_t* out, int B, int C, int Hs, int Ws, int H,
-                                    int W, int P, int Kp, int vec, const pvr::MixRow* mix, hipStream_t s) {
+                                    int W, int P, int Kp, int vec, const pvr::MixRow* mix, const int* keep, int n_keep,
+                                    hipStream_t s) {
   using namespace pvr;
   if (mix && reinterpret_cast<uintptr_t>(mix) % 16) return hipErrorInvalidValue;
   if (Kp % 8 || P <= 0 || C < 1 || C > 4 || H % P || W % P || Kp < C * P * P || Hs < 1 || Ws < 1) return hipErrorInvalidValue;
   if (!geom && (Hs != H || Ws != W)) return hipErrorInvalidValue;
   if (vec && (geom || sx != 1 || P % 8 || reinterpret_cast<uintptr_t>(img) % 8 || sb % 8 || sc % 8 || sy % 8))
     return hipErrorInvalidValue;
-  const int64_t total = (int64_t)B * (H / P) * (W / P) * (Kp / 8);
+  if (keep && (n_keep < 1 || n_keep > (H / P) * (W / P))) return hipErrorInvalidValue;
+  const int64_t total = (int64_t)B * (keep ? n_keep : (H / P) * (W / P)) * (Kp / 8);
   if (total <= 0) return hipSuccess;
   int64_t blocks = (total + 255) / 256;
   if (blocks > 2048) blocks = 2048;  // 8 blocks per CU: a block's 256 x C table entries serve ~9 trips of its threads at b256
@@ -830,10 +959,12 @@ extern "C" hipError_t pvr_im2col_u8(const uint8_t* img, int64_t sb, int64_t sc, 
     nrm.mean[c] = c < C ? mean[c] : 0.f;
     nrm.stdv[c] = c < C ? stdv[c] : 1.f;
   }
-  const auto kern = mix ? (geom ? im2col_u8_kernel<true, true> : im2col_u8_kernel<false, true>)
-                        : (geom ? im2col_u8_kernel<true, false> : im2col_u8_kernel<false, false>);
+  const auto kern = keep ? (mix ? (geom ? im2col_u8_kernel<true, true, true> : im2col_u8_kernel<false, true, true>)
+                                 : (geom ? im2col_u8_kernel<true, false, true> : im2col_u8_kernel<false, false, true>))
+                         : (mix ? (geom ? im2col_u8_kernel<true, true> : im2col_u8_kernel<false, true>)
+                                : (geom ? im2col_u8_kernel<true, false> : im2col_u8_kernel<false, false>));
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, s, img, sb, sc, sy, sx, nrm, geom, out, B, C, Hs, Ws, H, W, P, Kp,
-                     vec, mix);
+                     vec, mix, keep, keep ? n_keep : 0);
   return hipGetLastError();
 }
 
@@ -848,13 +979,14 @@ extern "C" hipError_t pvr_cls_rows(const float* cls, const float* pos, uint16_t*
 }
 
 extern "C" hipError_t pvr_patch_bwd(const uint16_t* dE, int B, int ntok, int D, float* ws, float* dpos, float* dcls,
-                                    uint16_t* dconv, float* dbias, pvr::DropSite drop, hipStream_t s) {
+                                    uint16_t* dconv, float* dbias, pvr::DropSite drop, const int* inv, int n_keep, hipStream_t s) {
   using namespace pvr;
   if (ntok * D <= 0 || B <= 0) return hipSuccess;
   if (D % 8) return hipErrorInvalidValue;
+  if (inv && (n_keep < 1 || n_keep > ntok - 1)) return hipErrorInvalidValue;
   const int G = (B + PB_BAT - 1) / PB_BAT;  // ws holds G * ntok * D floats (host-checked)
-  hipLaunchKernelGGL(patch_bwd_kernel, dim3((ntok * (D / 8) + 255) / 256, G), dim3(256), 0, s, dE, B, ntok, D, ws, dconv,
-                     drop.seed, drop.offset, drop.thr, drop.scale);
+  hipLaunchKernelGGL(inv ? patch_bwd_kernel<true> : patch_bwd_kernel<false>, dim3((ntok * (D / 8) + 255) / 256, G), dim3(256), 0, s, dE,
+                     B, ntok, D, ws, dconv, drop.seed, drop.offset, drop.thr, drop.scale, inv, inv ? n_keep : 0);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   // ws also holds the conv-bias partials of the reduction's token blocks, after the group sums

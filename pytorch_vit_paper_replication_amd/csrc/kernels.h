@@ -164,18 +164,31 @@ hipError_t pvr_colsum(const uint16_t* dy, int64_t ld, int rows, int N, float* db
 hipError_t pvr_drop_path_scale(pvr::DropSite dpath, float* s_out, int B, hipStream_t s);
 // d0/d1/d2[c % seg] += sum over the R rows of part[R][C] (row order: deterministic)
 hipError_t pvr_rows_reduce(const float* part, int R, int C, int seg, float* d0, float* d1, float* d2, hipStream_t s);
-// mix (both patchify kernels; null: none): the batch's MixRow plan, host-validated (bindings.cpp mix_rows)
+// Patch dropout: keep [B][n_keep] (the kept patch indices of each sample, strictly ascending) and inv
+// [B][np] (a patch's slot in its sample's keep row, -1: dropped) from the counter hash: sample b keeps the
+// n_keep patches j with the smallest (rng_hash(*seed + offset, b * np + j), j) pairs. np <= 4096,
+// 1 <= n_keep <= np, B * np < 2^32.
+hipError_t pvr_patch_keep(const uint64_t* seed, uint64_t offset, int B, int np, int n_keep, int* keep, int* inv, hipStream_t s);
+// out f32 [B][n_keep + 1][D]: row 1 + s of sample b = pos[keep[b][s] + 1], row 0 = pos[0] (pos [np + 1][D]; D % 4 == 0,
+// 16-byte aligned bases): the embedding GEMM's position addend under patch dropout
+hipError_t pvr_pos_gather(const float* pos, const int* keep, float* out, int B, int np, int n_keep, int D, hipStream_t s);
+// mix (both patchify kernels; null: none): the batch's MixRow plan, host-validated (bindings.cpp mix_rows).
+// keep (both; null: every patch): pvr_patch_keep's table; out then has B * n_keep rows, row r = patch
+// keep[r] of sample r / n_keep
 hipError_t pvr_im2col(const float* img, uint16_t* out, int B, int C, int H, int W, int P, int Kp, const pvr::MixRow* mix,
-                      hipStream_t s);
+                      const int* keep, int n_keep, hipStream_t s);
 // strides in elements (= bytes); geom null: Hs == H and Ws == W. `vec`: the caller has checked the
 // 8-byte load conditions on the base pointer and strides (bindings.cpp im2col_u8).
 hipError_t pvr_im2col_u8(const uint8_t* img, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float* mean, const float* stdv,
                          const float* geom, uint16_t* out, int B, int C, int Hs, int Ws, int H, int W, int P, int Kp, int vec,
-                         const pvr::MixRow* mix, hipStream_t s);
+                         const pvr::MixRow* mix, const int* keep, int n_keep, hipStream_t s);
 hipError_t pvr_cls_rows(const float* cls, const float* pos, uint16_t* out, int B, int D, int64_t row_stride, pvr::DropSite drop,
                         hipStream_t s);
+// inv (null: none): pvr_patch_keep's slot table of a patch-dropout step. dE is then the compact
+// [B][n_keep + 1][D] gradient (the dropout mask is that of the compact element index) and dconv
+// [B * n_keep][D]; dpos / ws keep their ntok = np + 1 positions, exact zeros where no sample kept a patch
 hipError_t pvr_patch_bwd(const uint16_t* dE, int B, int ntok, int D, float* ws, float* dpos, float* dcls, uint16_t* dconv,
-                         float* dbias, pvr::DropSite drop, hipStream_t s);
+                         float* dbias, pvr::DropSite drop, const int* inv, int n_keep, hipStream_t s);
 int pvr_patch_bwd_groups(int B);
 // floats of the scratch pvr_patch_bwd needs: the group sums and the conv-bias partials
 int64_t pvr_patch_bwd_ws_floats(int B, int ntok, int D);

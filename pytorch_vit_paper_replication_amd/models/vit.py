@@ -28,8 +28,22 @@ from torch import nn
 from .. import _ext
 
 
+def patch_keep_count(n_p: int, rate: float) -> int:
+    """Patches each sample keeps under patch dropout at ``rate``: ``max(1, n_p - floor(rate * n_p))`` (Python
+    double arithmetic). ``n_p`` itself means off."""
+    rate = float(rate)
+    if not 0.0 <= rate < 1.0:
+        raise ValueError(f"patch-dropout rate must be in [0, 1), got {rate}")
+    return max(1, n_p - int(math.floor(rate * n_p)))
+
+
 class PatchEmbedding(nn.Module):
-    """Image -> [B, N+1, D] patch + CLS + position embeddings (reference models/vit.py:5-67)."""
+    """Image -> [B, N+1, D] patch + CLS + position embeddings (reference models/vit.py:5-67).
+
+    ``patch_keep`` (attribute, default 0 = off; set by :meth:`ViT.set_patch_dropout`): patch dropout. In
+    training (grad mode on) each sample keeps that many of its patch tokens, in raster order, behind the
+    class token: the output is ``[B, patch_keep + 1, D]``. The position embedding is added before the
+    gather, the embedding dropout runs after it."""
 
     def __init__(self, image_size: int, color_channels: int = 3, patch_size: int = 16,
                  embedding_dropout: float = 0.1, embedding_dim: int = 768):
@@ -46,13 +60,32 @@ class PatchEmbedding(nn.Module):
         self.position_embedding = nn.Parameter(torch.rand(1, self.number_of_patches + 1, embedding_dim),
                                                requires_grad=True)
         self.dropout = nn.Dropout(p=embedding_dropout)
+        self.patch_keep = 0
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         b = x.shape[0]
         cls = self.class_token.expand(b, -1, -1)
         x = self.patch_and_flatten(x).permute(0, 2, 1)
         x = torch.cat((cls, x), dim=1) + self.position_embedding
+        n_keep = self.patch_keep_active()
+        if n_keep:
+            keep = self._draw_patch_keep(b, self.number_of_patches, n_keep, x.device).to(device=x.device, dtype=torch.int64)
+            rows = torch.cat((torch.zeros(b, 1, dtype=torch.int64, device=x.device), keep + 1), dim=1)  # [0] + (keep + 1)
+            x = torch.gather(x, 1, rows.unsqueeze(-1).expand(-1, -1, x.shape[-1]))
         return self.dropout(x)
+
+    def patch_keep_active(self) -> int:
+        """Patches per sample this forward keeps: ``patch_keep`` in training with grad mode on, else 0 (every
+        patch: eval, ``no_grad`` and ``inference_mode`` never drop)."""
+        n_keep = int(getattr(self, "patch_keep", 0))
+        on = n_keep and n_keep < self.number_of_patches and self.training and torch.is_grad_enabled()
+        return n_keep if on else 0
+
+    def _draw_patch_keep(self, batch: int, n_p: int, n_keep: int, device) -> torch.Tensor:
+        """The kept patch indices ``[batch, n_keep]``, ascending per sample, on the reference path: a uniform
+        random subset from torch's RNG (the fused path ranks counter-hash keys instead, ``ops/fused_vit.py``
+        ``patch_keep``; tests override this method to replay its table)."""
+        return torch.rand(batch, n_p, device=device).argsort(dim=1)[:, :n_keep].sort(dim=1).values
 
 
 class SelfAttention(nn.Module):
@@ -282,6 +315,32 @@ class ViT(nn.Module):
         """The per-block rates in effect (all 0 without :meth:`set_drop_path`)."""
         return [float(getattr(blk, "drop_path", 0.0)) for blk in self.transformer_encoder]
 
+    # ------------------------------------------------------------------ patch dropout
+    def set_patch_dropout(self, rate: float) -> "ViT":
+        """Patch dropout (PatchDropout, Liu et al. 2022; the token subsetting of FLIP / MAE pre-training): in
+        training every sample keeps a random ``n_keep = max(1, n_p - floor(rate * n_p))`` of its ``n_p`` patch
+        tokens, in raster order, behind the class token (always kept), and the encoder runs at
+        ``N' = n_keep + 1`` tokens: its cost falls by about the token ratio. ``rate`` is in ``[0, 1)``;
+        ``rate = 0`` (or any rate with ``n_keep == n_p``) turns it off, and the model then runs exactly as
+        before. ``model.eval()``, ``no_grad`` and ``inference_mode`` forwards never drop: their outputs are
+        those of the same weights without the option. The classifier-free backbone
+        (``models/vit_no_classifier.py``) returns ``[B, N', D]`` in training.
+
+        On the fused path the subset comes from the counter hash of the dropout masks (site
+        ``PATCH_DROP_SITE``, the step's value of the device counter, so graph replay, resume and DDP work):
+        a sample keeps the ``n_keep`` patches with the smallest ``(hash, index)`` pairs; the patchify
+        kernels gather only those, the position embedding is gathered to match, the dropout masks are those
+        of the compact token index, and the patch-embedding backward scatters through the inverse table
+        (the position-embedding gradient is exactly zero where no sample kept a patch). Elsewhere
+        :meth:`PatchEmbedding._draw_patch_keep` draws the subset from torch's RNG. Not with
+        :meth:`enable_fp8`. The constructor signature and ``state_dict()`` are unchanged; the rate is kept
+        in ``config["patch_dropout"]``."""
+        pe = self.patch_embedding_block
+        n_keep = patch_keep_count(pe.number_of_patches, rate)
+        pe.patch_keep = n_keep if n_keep < pe.number_of_patches else 0
+        self.config["patch_dropout"] = float(rate)
+        return self
+
     # ------------------------------------------------------------------ uint8 input
     def set_device_input(self, spec) -> "ViT":
         """Accept raw ``uint8 [B, 3, Hs, Ws]`` batches (contiguous or ``channels_last``): ``spec`` is a
@@ -411,6 +470,12 @@ class ViT(nn.Module):
             raise NotImplementedError(
                 "enable_fp8() does not combine with set_drop_path(): the fp8 gradient copies of the out-projection and "
                 "fc2 dgrads would have to be taken from the drop-path-scaled gradients; turn one of the two off")
+        pe = self.patch_embedding_block
+        n_keep = pe.patch_keep_active()  # patch dropout: patches per sample this forward keeps (0: all)
+        if n_keep and getattr(self, "_fp8_cfg", None) is not None:
+            raise NotImplementedError(
+                "enable_fp8() does not combine with set_patch_dropout(): the fp8 scaling state is sized by the token "
+                "count, which would differ between training and evaluation; turn one of the two off")
         for p in self.parameters():
             if p.device != dev:
                 raise RuntimeError(f"input is on {dev} but model parameters are on {p.device}")
@@ -427,20 +492,19 @@ class ViT(nn.Module):
         if grad:
             store.prepare_grads()
         need_seed = training and (c["mlp_dropout"] > 0 or c["embedding_dropout"] > 0 or c["attn_dropout"] > 0
-                                  or any(p > 0 for p in dp_rates))
+                                  or any(p > 0 for p in dp_rates) or n_keep > 0)
         seed = self._dropout_seed(dev) if need_seed else None
-        pe = self.patch_embedding_block
         conv = pe.patch_and_flatten[0]
         if pre is None:
             tokens = PatchEmbedFn.apply(x, c["patch_size"], store, seed, pe.dropout.p, training,
-                                        conv.weight, conv.bias, pe.class_token, pe.position_embedding, mix)
+                                        conv.weight, conv.bias, pe.class_token, pe.position_embedding, mix, n_keep)
         else:
             mean, std, geom = pre
             tokens = PatchEmbedU8Fn.apply(x, geom, mean, std, (c["image_size"], c["image_size"]), c["patch_size"], store, seed,
                                           pe.dropout.p, training, conv.weight, conv.bias, pe.class_token,
-                                          pe.position_embedding, mix)
+                                          pe.position_embedding, mix, n_keep)
         B = x.shape[0]
-        N = pe.number_of_patches + 1
+        N = (n_keep or pe.number_of_patches) + 1  # the encoder's tokens per sample
         f8 = self._fp8_state(dev, B * N)
         if f8 is not None:
             f8.begin_step(training)

@@ -1,7 +1,9 @@
 """ViT backbone without the classifier head (reference models/vit_no_classifier.py:172-226).
 
 ``forward`` returns the final-LayerNorm'd full token sequence ``[B, N+1, D]``; the state_dict is the
-full ViT's minus ``classifier.*``. The building blocks are shared with :mod:`.vit` (the reference keeps
+full ViT's minus ``classifier.*``. With ``set_patch_dropout(rate)`` a training forward returns the kept
+tokens only, ``[B, N'+1, D]`` with ``N' = max(1, N - floor(rate * N))`` (class token first, kept patches in
+raster order); eval, ``no_grad`` and ``inference_mode`` forwards return every token. The building blocks are shared with :mod:`.vit` (the reference keeps
 verbatim copies; here there is one implementation).
 """
 from __future__ import annotations

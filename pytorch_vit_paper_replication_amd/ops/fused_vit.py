@@ -28,6 +28,9 @@ ATTN_SITE = 1 << 20  # dropout site of block i's attention probabilities: ATTN_S
 # stochastic depth (drop path): block i's attention branch draws its per-sample keep decisions at site
 # DROP_PATH_SITE + 2 i, its MLP branch at DROP_PATH_SITE + 2 i + 1 (disjoint from 0 .. 2 L and ATTN_SITE + i)
 DROP_PATH_SITE = 1 << 21
+# patch dropout: the keys that rank a sample's patches (csrc/elementwise.hip patch_keep_kernel) are the
+# hashes of site PATCH_DROP_SITE (disjoint from 0 .. 2 L, ATTN_SITE + i and DROP_PATH_SITE + k)
+PATCH_DROP_SITE = 1 << 22
 
 
 # Test hook: called as DGRAD_TAP(which, output) after every encoder-block dgrad GEMM (which = 0 fc2,
@@ -60,14 +63,35 @@ def _patch_geometry(C, H, W, patch):
     return n_p, kc, (kc + 63) // 64 * 64
 
 
-def _patch_embed_fwd(ctx, patches, B, n_p, kc, kp, store, seed, p_drop, training, conv_w, conv_b, cls, pos):
+def patch_keep(seed, B: int, n_p: int, n_keep: int):
+    """Patch dropout's table for a step: ``(keep, inv)`` of ``ext.patch_keep_table`` at the counter value
+    ``seed`` (None when ``n_keep`` is 0 = off). ``keep`` int32 [B, n_keep]: the kept patches of each sample,
+    ascending; ``inv`` int32 [B, n_p]: a patch's row in ``keep``, -1 if dropped."""
+    if not n_keep:
+        return None
+    if n_p > 4096 or B * n_p >= 2 ** 32:
+        raise ValueError(f"patch dropout takes at most 4096 patches per image and B * n_p < 2^32, got {B} x {n_p}")
+    return _ext.ext().patch_keep_table(seed, PATCH_DROP_SITE << SITE_SHIFT, B, n_p, n_keep)
+
+
+def _keep_arg(table):
+    """The patchify kernels' ``keep`` argument for a :func:`patch_keep` table ({}: none, today's call)."""
+    return {} if table is None else dict(keep=table[0])
+
+
+def _patch_embed_fwd(ctx, patches, B, n_p, kc, kp, store, seed, p_drop, training, conv_w, conv_b, cls, pos, table=None):
     """Patch rows [B*n_p, kp] bf16 -> tokens [B*(n_p+1), D]: the embedding GEMM with the position
     addend and dropout, the CLS rows, and what the backward needs. Shared by the float and the
-    uint8 entry (PatchEmbedFn / PatchEmbedU8Fn), which differ only in how ``patches`` is built."""
+    uint8 entry (PatchEmbedFn / PatchEmbedU8Fn), which differ only in how ``patches`` is built.
+
+    ``table`` (patch dropout, :func:`patch_keep`): ``patches`` holds the kept rows only, [B*n_keep, kp], and
+    the tokens are the compact [B*(n_keep+1), D]; the position addend is gathered per row (one fp32
+    [B*(n_keep+1), D] tensor), and the dropout masks are those of the compact element index."""
     ext = _ext.ext()
     dev = patches.device
     D = conv_w.shape[0]
     ntok = n_p + 1
+    rows = ntok if table is None else table[0].shape[1] + 1  # token rows per sample
     w16 = store.bf16(conv_w).reshape(D, kc)
     if kp != kc:
         if kc % 4 == 0:
@@ -76,30 +100,36 @@ def _patch_embed_fwd(ctx, patches, B, n_p, kc, kp, store, seed, p_drop, training
             w16 = w16p
         else:  # odd patch sizes (kc = 3 * P * P odd): plain zero padding
             w16 = torch.nn.functional.pad(w16, (0, kp - kc))
-    tokens = torch.empty(B * ntok, D, dtype=torch.bfloat16, device=dev)
+    tokens = torch.empty(B * rows, D, dtype=torch.bfloat16, device=dev)
     drop = site_drop(seed, 0, p_drop, training)
-    gemm.linear_fwd(patches, w16, conv_b, addend=pos.reshape(ntok, D), addend_period=ntok,
-                    row_remap=(n_p, ntok, 1), drop=drop, out=tokens)
+    if table is None:
+        addend, period = pos.reshape(ntok, D), ntok
+    else:
+        addend, period = ext.pos_gather(pos.reshape(ntok, D), table[0]), B * rows
+    gemm.linear_fwd(patches, w16, conv_b, addend=addend, addend_period=period,
+                    row_remap=(rows - 1, rows, 1), drop=drop, out=tokens)
     dseed, doff, dp = gemm._drop_args(drop)
-    ext.cls_rows(cls.reshape(D), pos.reshape(ntok, D)[0].contiguous(), tokens, B, D, ntok * D, dseed, doff, dp)
+    ext.cls_rows(cls.reshape(D), pos.reshape(ntok, D)[0].contiguous(), tokens, B, D, rows * D, dseed, doff, dp)
     ctx.save_for_backward(patches)
-    ctx.meta = (store, drop, B, ntok, D, kc, kp, conv_w, conv_b, cls, pos)
+    ctx.meta = (store, drop, B, ntok, D, kc, kp, conv_w, conv_b, cls, pos, None if table is None else table[1])
     return tokens
 
 
 def _patch_embed_bwd(ctx, dtokens) -> None:
     ext = _ext.ext()
     (patches,) = ctx.saved_tensors
-    store, drop, B, ntok, D, kc, kp, conv_w, conv_b, cls, pos = ctx.meta
+    store, drop, B, ntok, D, kc, kp, conv_w, conv_b, cls, pos, inv = ctx.meta
     dtokens = dtokens.contiguous()
     gpos = store.grad_dest(pos)
     gcls = store.grad_dest(cls)
     gb = store.grad_dest(conv_b)
     gw = store.grad_dest(conv_w)
-    dconv = torch.empty(B * (ntok - 1), D, dtype=torch.bfloat16, device=dtokens.device) if gw is not None else None
+    n_keep = patches.shape[0] // B if inv is not None else 0  # patch dropout: dtokens / dconv are the compact tensors
+    dconv = torch.empty(patches.shape[0], D, dtype=torch.bfloat16, device=dtokens.device) if gw is not None else None
     dseed, doff, dp = gemm._drop_args(drop)
     ext.patch_bwd(dtokens, B, ntok, D, None if gpos is None else gpos.view(-1),
-                  None if gcls is None else gcls.view(-1), dconv, gb, dseed, doff, dp)
+                  None if gcls is None else gcls.view(-1), dconv, gb, dseed, doff, dp,
+                  **({} if inv is None else dict(inv=inv, n_keep=n_keep)))
     if gw is not None:  # K padded to kp in patches; the reduction writes the first kc columns
         gemm.linear_wgrad(dconv, patches, gw.view(D, kc))
     store.grad_ready([conv_w, conv_b, cls, pos])
@@ -118,18 +148,19 @@ class PatchEmbedFn(torch.autograd.Function):
     """``mix`` (optional ``MixPlan``): mixup / CutMix inside the gather, here and in PatchEmbedU8Fn."""
 
     @staticmethod
-    def forward(ctx, img, patch, store, seed, p_drop, training, conv_w, conv_b, cls, pos, mix=None):
+    def forward(ctx, img, patch, store, seed, p_drop, training, conv_w, conv_b, cls, pos, mix=None, n_keep=0):
         img = img.float().contiguous()
         B, C, H, W = img.shape
         n_p, kc, kp = _patch_geometry(C, H, W, patch)
-        patches = torch.empty(B * n_p, kp, dtype=torch.bfloat16, device=img.device)
-        _ext.ext().im2col(img, patches, patch, kp, **_mix_args(mix, B, (H, W), img.device))
-        return _patch_embed_fwd(ctx, patches, B, n_p, kc, kp, store, seed, p_drop, training, conv_w, conv_b, cls, pos)
+        table = patch_keep(seed, B, n_p, n_keep)
+        patches = torch.empty(B * (n_keep or n_p), kp, dtype=torch.bfloat16, device=img.device)
+        _ext.ext().im2col(img, patches, patch, kp, **_mix_args(mix, B, (H, W), img.device), **_keep_arg(table))
+        return _patch_embed_fwd(ctx, patches, B, n_p, kc, kp, store, seed, p_drop, training, conv_w, conv_b, cls, pos, table)
 
     @staticmethod
     def backward(ctx, dtokens):
         _patch_embed_bwd(ctx, dtokens)
-        return (None,) * 11
+        return (None,) * 12
 
 
 class PatchEmbedU8Fn(torch.autograd.Function):
@@ -139,18 +170,20 @@ class PatchEmbedU8Fn(torch.autograd.Function):
     while it writes the patch rows (data/device_input.py). ``geom`` None needs Hs x Ws == H x W."""
 
     @staticmethod
-    def forward(ctx, img, geom, mean, std, size, patch, store, seed, p_drop, training, conv_w, conv_b, cls, pos, mix=None):
+    def forward(ctx, img, geom, mean, std, size, patch, store, seed, p_drop, training, conv_w, conv_b, cls, pos, mix=None, n_keep=0):
         B, C = img.shape[0], img.shape[1]
         H, W = size
         n_p, kc, kp = _patch_geometry(C, H, W, patch)
-        patches = torch.empty(B * n_p, kp, dtype=torch.bfloat16, device=img.device)
-        _ext.ext().im2col_u8(img, patches, list(mean), list(std), geom, H, W, patch, kp, **_mix_args(mix, B, (H, W), img.device))
-        return _patch_embed_fwd(ctx, patches, B, n_p, kc, kp, store, seed, p_drop, training, conv_w, conv_b, cls, pos)
+        table = patch_keep(seed, B, n_p, n_keep)
+        patches = torch.empty(B * (n_keep or n_p), kp, dtype=torch.bfloat16, device=img.device)
+        _ext.ext().im2col_u8(img, patches, list(mean), list(std), geom, H, W, patch, kp, **_mix_args(mix, B, (H, W), img.device),
+                             **_keep_arg(table))
+        return _patch_embed_fwd(ctx, patches, B, n_p, kc, kp, store, seed, p_drop, training, conv_w, conv_b, cls, pos, table)
 
     @staticmethod
     def backward(ctx, dtokens):
         _patch_embed_bwd(ctx, dtokens)
-        return (None,) * 15
+        return (None,) * 16
 
 
 # test hook: bf16 outputs left unwritten on the fp8 path (only their fp8 copies are consumed) are
