@@ -416,6 +416,9 @@ void splitk_epilogue(torch::Tensor ws, int64_t S, torch::Tensor out, c10::option
 
 void cast_f32_bf16(torch::Tensor in, torch::Tensor out) {
   TORCH_CHECK(in.is_contiguous() && out.is_contiguous() && in.numel() == out.numel(), "cast: shape/contiguity");
+  TORCH_CHECK(in.device() == out.device() && reinterpret_cast<uintptr_t>(in.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(out.data_ptr()) % 8 == 0,
+              "cast: in (16-byte aligned) and out (8-byte aligned) on one GPU");
   check(pvr_cast_f32_bf16(f32(in, "in"), bf_mut(out, "out"), in.numel(), stream()), "cast_f32_bf16");
 }
 
@@ -696,13 +699,41 @@ torch::Tensor xent(torch::Tensor logits, torch::Tensor labels, c10::optional<tor
   return loss;
 }
 
-void grad_norm(torch::Tensor g, double max_norm, torch::Tensor workspace, torch::Tensor out) {
-  TORCH_CHECK(g.is_contiguous(), "grad_norm: flat grad must be contiguous");
-  TORCH_CHECK(workspace.numel() >= pvr_norm_partial_blocks(), "grad_norm: workspace too small");
-  check(pvr_grad_norm(f32(g, "g"), g.numel(), (float)max_norm, f32_mut(workspace, "ws"), f32_mut(out, "out"), stream()), "grad_norm");
+// The optimizer kernels take raw pointers and element counts: every tensor whose pointer a kernel
+// dereferences is checked here, before any launch, for what the kernel assumes of it.
+// A flat fp32 buffer read or written as float4: float32, contiguous, 16-byte aligned, on `like`'s device.
+void flat_f32(const torch::Tensor& t, const torch::Tensor& like, const char* who, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device() && t.scalar_type() == torch::kFloat32 && t.is_contiguous(), who, ": ", name,
+              " must be a contiguous float32 tensor on the GPU of the other buffers");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, who, ": ", name, " must be 16-byte aligned");
+}
+// A bf16 shadow with the layout of p, written 4 (shadow) or 8 (W^T) values at a time
+void flat_bf16(const torch::Tensor& t, const torch::Tensor& like, int64_t align, const char* who, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device() && t.scalar_type() == torch::kBFloat16 && t.is_contiguous(), who, ": ", name,
+              " must be a contiguous bfloat16 tensor on the parameters' GPU");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % align == 0, who, ": ", name, " must be ", align, "-byte aligned");
+}
+// {norm, clip coefficient, non-finite flag}: what grad_norm writes and the Adam kernels read
+float* clip_triple(const torch::Tensor& t, const torch::Tensor& like, const char* who, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device() && t.scalar_type() == torch::kFloat32 && t.is_contiguous() && t.numel() >= 3, who,
+              ": ", name, " must be a contiguous float32 tensor of at least 3 elements on the GPU of the other buffers");
+  return t.data_ptr<float>();
+}
+const float* opt_clip(const c10::optional<torch::Tensor>& clip, const torch::Tensor& like, const char* who) {
+  return clip.has_value() && clip->defined() ? clip_triple(*clip, like, who, "clip") : nullptr;
 }
 
-// Param-group table float32 [G][8] (kernels.h AdamGroup): a CUDA tensor is read by the kernel
+void grad_norm(torch::Tensor g, double max_norm, torch::Tensor workspace, torch::Tensor out) {
+  TORCH_CHECK(g.is_cuda(), "grad_norm: g must be a GPU tensor");
+  flat_f32(g, g, "grad_norm", "g");
+  TORCH_CHECK(workspace.is_cuda() && workspace.device() == g.device() && workspace.scalar_type() == torch::kFloat32 &&
+                  workspace.is_contiguous() && workspace.numel() >= pvr_norm_partial_blocks(),
+              "grad_norm: workspace must be a contiguous float32 tensor of at least ", pvr_norm_partial_blocks(), " elements on g's GPU");
+  float* po = clip_triple(out, g, "grad_norm", "out");
+  check(pvr_grad_norm(g.data_ptr<float>(), g.numel(), (float)max_norm, workspace.data_ptr<float>(), po, stream()), "grad_norm");
+}
+
+// Param-group table float32 [G][10] (kernels.h AdamGroup): a CUDA tensor is read by the kernel
 // (graph-captured steps); a CPU tensor is copied into the launch's kernel arguments (G <= 8), so an
 // eager step needs no host-to-device copy of its per-step lr / bias corrections.
 struct GroupTable {
@@ -710,13 +741,15 @@ struct GroupTable {
   const pvr::AdamGroup* host = nullptr;
   int n = 0;
 };
-GroupTable group_table(const torch::Tensor& groups, const char* who) {
-  TORCH_CHECK(groups.scalar_type() == torch::kFloat32 && groups.dim() == 2 && groups.size(1) == 8 && groups.is_contiguous(), who,
-              ": groups must be contiguous float32 [G, 8]");
+GroupTable group_table(const torch::Tensor& groups, const torch::Tensor& p, const char* who) {
+  TORCH_CHECK(groups.scalar_type() == torch::kFloat32 && groups.dim() == 2 && groups.size(1) == pvr::ADAM_GROUP_COLS &&
+                  groups.is_contiguous(),
+              who, ": groups must be contiguous float32 [G, ", pvr::ADAM_GROUP_COLS, "]");
   GroupTable t;
   t.n = (int)groups.size(0);
   auto* ptr = reinterpret_cast<const pvr::AdamGroup*>(groups.data_ptr<float>());
   if (groups.is_cuda()) {
+    TORCH_CHECK(groups.device() == p.device() && t.n >= 1, who, ": a device group table holds >= 1 groups on the parameters' GPU");
     t.dev = ptr;
   } else {
     TORCH_CHECK(t.n >= 1 && t.n <= 8, who, ": a host group table holds 1..8 groups (pass a device table for more)");
@@ -751,16 +784,29 @@ pvr::AdamEma ema_args(const torch::Tensor& p, c10::optional<torch::Tensor>& ema,
 void adam(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, c10::optional<torch::Tensor> shadow, torch::Tensor seg_start,
           torch::Tensor seg_group, torch::Tensor groups, c10::optional<torch::Tensor> clip, bool skip_nonfinite,
           c10::optional<torch::Tensor> ema, c10::optional<torch::Tensor> ema_pair) {
+  TORCH_CHECK(p.is_cuda(), "adam: p must be a GPU tensor");
+  flat_f32(p, p, "adam", "p"); flat_f32(g, p, "adam", "g"); flat_f32(m, p, "adam", "m"); flat_f32(v, p, "adam", "v");
   TORCH_CHECK(p.numel() == g.numel() && p.numel() == m.numel() && p.numel() == v.numel(), "adam: size mismatch");
-  const GroupTable gt = group_table(groups, "adam");
+  TORCH_CHECK(p.numel() % 4 == 0, "adam: the flat buffers hold a multiple of 4 elements (the kernel works in float4), got ", p.numel());
+  const GroupTable gt = group_table(groups, p, "adam");
   TORCH_CHECK(seg_start.scalar_type() == torch::kInt64 && seg_group.scalar_type() == torch::kInt32, "adam: segment table dtypes");
+  TORCH_CHECK(seg_start.is_cuda() && seg_group.is_cuda() && seg_start.device() == p.device() && seg_group.device() == p.device() &&
+                  seg_start.is_contiguous() && seg_group.is_contiguous(),
+              "adam: seg_start / seg_group must be contiguous tensors on the parameters' GPU");
+  TORCH_CHECK(seg_start.numel() >= 1 && seg_start.numel() == seg_group.numel() && seg_start.numel() < (int64_t(1) << 31),
+              "adam: seg_start / seg_group must hold the same number (>= 1) of segments, got ", seg_start.numel(), " and ",
+              seg_group.numel());
   uint16_t* sh = nullptr;
-  if (shadow.has_value() && shadow->defined()) sh = const_cast<uint16_t*>(bf(*shadow, "shadow"));
-  if (ema.has_value() && ema->defined()) TORCH_CHECK(p.is_contiguous(), "adam: contiguous parameters");
+  if (shadow.has_value() && shadow->defined()) {
+    flat_bf16(*shadow, p, 8, "adam", "shadow");
+    TORCH_CHECK(shadow->numel() == p.numel(), "adam: shadow must hold the parameters' ", p.numel(), " elements, got ", shadow->numel());
+    sh = reinterpret_cast<uint16_t*>(shadow->data_ptr());
+  }
+  const float* pc = opt_clip(clip, p, "adam");
   const pvr::AdamEma ea = ema_args(p, ema, ema_pair, "adam");
-  check(pvr_adam(f32_mut(p, "p"), f32(g, "g"), f32_mut(m, "m"), f32_mut(v, "v"), sh, p.numel(), seg_start.data_ptr<int64_t>(),
-                 seg_group.data_ptr<int>(), (int)seg_start.numel(), gt.dev, gt.host, gt.n, opt_ptr<const float>(clip), skip_nonfinite ? 1 : 0, ea,
-                 stream()),
+  check(pvr_adam(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), sh, p.numel(),
+                 seg_start.data_ptr<int64_t>(), seg_group.data_ptr<int>(), (int)seg_start.numel(), gt.dev, gt.host, gt.n, pc,
+                 skip_nonfinite ? 1 : 0, ea, stream()),
         "adam");
 }
 
@@ -771,20 +817,26 @@ void adam_t(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, 
             torch::Tensor tmeta, int64_t ntiles, torch::Tensor fmeta, int64_t flat4, torch::Tensor groups,
             c10::optional<torch::Tensor> clip, bool skip_nonfinite, c10::optional<torch::Tensor> ema,
             c10::optional<torch::Tensor> ema_pair) {
+  TORCH_CHECK(p.is_cuda(), "adam_t: p must be a GPU tensor");
+  flat_f32(p, p, "adam_t", "p"); flat_f32(g, p, "adam_t", "g"); flat_f32(m, p, "adam_t", "m"); flat_f32(v, p, "adam_t", "v");
+  flat_bf16(shadow, p, 8, "adam_t", "shadow");
+  flat_bf16(shadow_t, p, 16, "adam_t", "shadow_t");
   TORCH_CHECK(p.numel() == g.numel() && p.numel() == m.numel() && p.numel() == v.numel() && shadow.numel() == p.numel(),
               "adam_t: size mismatch");
-  const GroupTable gt = group_table(groups, "adam_t");
-  TORCH_CHECK(tmeta.is_cuda() && tmeta.scalar_type() == torch::kInt64 && tmeta.dim() == 2 && tmeta.size(1) == 6 && tmeta.is_contiguous(),
-              "adam_t: tmeta int64 [n][6]");
-  TORCH_CHECK(fmeta.is_cuda() && fmeta.scalar_type() == torch::kInt64 && fmeta.dim() == 2 && fmeta.size(1) == 4 && fmeta.is_contiguous(),
-              "adam_t: fmeta int64 [n][4]");
-  TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && m.is_contiguous() && v.is_contiguous() && shadow.is_contiguous() &&
-                  shadow_t.is_contiguous(),
-              "adam_t: contiguous buffers");
+  const GroupTable gt = group_table(groups, p, "adam_t");
+  TORCH_CHECK(tmeta.is_cuda() && tmeta.device() == p.device() && tmeta.scalar_type() == torch::kInt64 && tmeta.dim() == 2 &&
+                  tmeta.size(0) >= 1 && tmeta.size(1) == 6 && tmeta.is_contiguous(),
+              "adam_t: tmeta int64 [n >= 1][6] on the parameters' GPU");
+  TORCH_CHECK(fmeta.is_cuda() && fmeta.device() == p.device() && fmeta.scalar_type() == torch::kInt64 && fmeta.dim() == 2 &&
+                  fmeta.size(0) >= 1 && fmeta.size(1) == 4 && fmeta.is_contiguous(),
+              "adam_t: fmeta int64 [n >= 1][4] on the parameters' GPU");
+  TORCH_CHECK(ntiles >= 1 && ntiles < (int64_t(1) << 31) && flat4 >= 0, "adam_t: ntiles >= 1 and flat4 >= 0");
+  const float* pc = opt_clip(clip, p, "adam_t");
   const pvr::AdamEma ea = ema_args(p, ema, ema_pair, "adam_t");
-  check(pvr_adam_t(f32_mut(p, "p"), f32(g, "g"), f32_mut(m, "m"), f32_mut(v, "v"), bf_mut(shadow, "shadow"), bf_mut(shadow_t, "shadow_t"),
+  check(pvr_adam_t(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
+                   reinterpret_cast<uint16_t*>(shadow.data_ptr()), reinterpret_cast<uint16_t*>(shadow_t.data_ptr()),
                    tmeta.data_ptr<int64_t>(), (int)tmeta.size(0), (int)ntiles, fmeta.data_ptr<int64_t>(), (int)fmeta.size(0), flat4,
-                   gt.dev, gt.host, gt.n, opt_ptr<const float>(clip), skip_nonfinite ? 1 : 0, ea, stream()),
+                   gt.dev, gt.host, gt.n, pc, skip_nonfinite ? 1 : 0, ea, stream()),
         "adam_t");
 }
 

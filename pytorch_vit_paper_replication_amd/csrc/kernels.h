@@ -11,14 +11,19 @@
 
 namespace pvr {
 
-// One row of the optimizer's param-group table, float32 [G][8] (optim/adam.py _group_array; the
-// last word holds an int)
+// One row of the optimizer's param-group table, float32 [G][10] (optim/adam.py _group_array; word
+// 7 holds an int). The weights of the new gradient in the moments, 1 - beta, are columns of their own,
+// rounded once from the host's double: 1.f - beta1 on the fp32 beta would carry beta's absolute
+// rounding (2^-25) as a relative error of 2^-25 / (1 - beta), 1.3e-5 at beta2 = 0.999, into v, which
+// bc2_sqrt (from the exact beta2) does not share.
 struct AdamGroup {
   float lr, beta1, beta2, eps, weight_decay;
   float bc1, bc2_sqrt;  // 1 - beta1^t, sqrt(1 - beta2^t)
   int decoupled;
+  float one_minus_beta1, one_minus_beta2;
 };
-static_assert(sizeof(AdamGroup) == 8 * sizeof(float), "AdamGroup is one float32 [8] row of the group table");
+constexpr int ADAM_GROUP_COLS = 10;
+static_assert(sizeof(AdamGroup) == ADAM_GROUP_COLS * sizeof(float), "AdamGroup is one float32 [10] row of the group table");
 
 // Model EMA updated inside the Adam pass: buf (fp32, the layout of p) becomes
 // decay * buf + one_minus_decay * p_new for every element the pass updates. pair: device

@@ -126,8 +126,8 @@ __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const 
       } else if (G.weight_decay != 0.f) {
         gr += G.weight_decay * pa[j];
       }
-      ma[j] = G.beta1 * ma[j] + (1.f - G.beta1) * gr;
-      va[j] = G.beta2 * va[j] + (1.f - G.beta2) * gr * gr;
+      ma[j] = G.beta1 * ma[j] + G.one_minus_beta1 * gr;
+      va[j] = G.beta2 * va[j] + G.one_minus_beta2 * gr * gr;
       const float denom = sqrtf(va[j]) / G.bc2_sqrt + G.eps;
       pa[j] -= step * ma[j] / denom;
     }
@@ -165,8 +165,8 @@ __device__ __forceinline__ void adam4(float4& pp, const float4& gg4, float4& mm,
     } else if (G.weight_decay != 0.f) {
       gr += G.weight_decay * pa[j];
     }
-    ma[j] = G.beta1 * ma[j] + (1.f - G.beta1) * gr;
-    va[j] = G.beta2 * va[j] + (1.f - G.beta2) * gr * gr;
+    ma[j] = G.beta1 * ma[j] + G.one_minus_beta1 * gr;
+    va[j] = G.beta2 * va[j] + G.one_minus_beta2 * gr * gr;
     const float denom = sqrtf(va[j]) / G.bc2_sqrt + G.eps;
     pa[j] -= step * ma[j] / denom;
   }

@@ -22,6 +22,7 @@ import torch
 
 from .. import _ext
 
+GROUP_COLS = 10  # csrc/kernels.h ADAM_GROUP_COLS
 
 
 def _store_of(params):
@@ -147,9 +148,12 @@ class FusedAdam(torch.optim.Optimizer):
         return self._ttables
 
     def _group_array(self, step: int, arr: Optional[np.ndarray] = None) -> np.ndarray:
+        """The kernels' group table (csrc/kernels.h AdamGroup), float32 [G, GROUP_COLS]. 1 - beta is
+        rounded once from the double here (columns 8, 9): formed in fp32 from the fp32 beta it would be
+        2^-25 / (1 - beta) off, 1.3e-5 at beta2 = 0.999."""
         G = len(self.param_groups)
         if arr is None:
-            arr = np.zeros((G, 8), dtype=np.float32)
+            arr = np.zeros((G, GROUP_COLS), dtype=np.float32)
         for i, g in enumerate(self.param_groups):
             b1, b2 = g["betas"]
             arr[i, 0] = float(g["lr"])
@@ -159,6 +163,8 @@ class FusedAdam(torch.optim.Optimizer):
             arr[i, 4] = g["weight_decay"]
             arr[i, 5] = 1.0 - b1 ** step
             arr[i, 6] = math.sqrt(1.0 - b2 ** step)
+            arr[i, 8] = 1.0 - b1
+            arr[i, 9] = 1.0 - b2
         arr.view(np.int32)[:, 7] = [int(bool(g["decoupled_weight_decay"])) for g in self.param_groups]
         return arr
 
@@ -176,18 +182,19 @@ class FusedAdam(torch.optim.Optimizer):
 
     def _alloc_table(self, device, ring: int = 4) -> None:
         G = len(self.param_groups)
-        # [G][8] group table, then the 2-float EMA pair (32-byte aligned behind it): one buffer, one copy
-        self._upload_dev = torch.zeros(G * 8 + 2, dtype=torch.float32, device=device)
-        self._table_dev = self._upload_dev[:G * 8].view(G, 8)
-        self._ema_pair_dev = self._upload_dev[G * 8:]
-        self._table_ring = [(torch.zeros(G * 8 + 2, dtype=torch.float32).pin_memory(), torch.cuda.Event()) for _ in range(ring)]
+        # [G][GROUP_COLS] group table, then the 2-float EMA pair (8-byte aligned behind it): one buffer, one copy
+        n = G * GROUP_COLS
+        self._upload_dev = torch.zeros(n + 2, dtype=torch.float32, device=device)
+        self._table_dev = self._upload_dev[:n].view(G, GROUP_COLS)
+        self._ema_pair_dev = self._upload_dev[n:]
+        self._table_ring = [(torch.zeros(n + 2, dtype=torch.float32).pin_memory(), torch.cuda.Event()) for _ in range(ring)]
 
     def _upload_table(self, step: int, ema_pair=None) -> None:
         host, ev = self._table_ring[self._ring_i % len(self._table_ring)]
         self._ring_i += 1
         ev.synchronize()  # the copy that last used this pinned buffer has executed
         arr = host.numpy()
-        self._group_array(max(step, 1), arr[:-2].reshape(-1, 8))
+        self._group_array(max(step, 1), arr[:-2].reshape(-1, GROUP_COLS))
         if ema_pair is not None:
             arr[-2:] = ema_pair
         self._upload_dev.copy_(host, non_blocking=True)

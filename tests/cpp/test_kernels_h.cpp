@@ -1,5 +1,5 @@
 // Host checks of the host-kernel interface header (csrc/kernels.h) under the plain host compiler:
-// it needs no device compiler, pvr::AdamGroup is exactly one float32 [8] row of the param-group table
+// it needs no device compiler, pvr::AdamGroup is exactly one float32 [10] row of the param-group table
 // that optim/adam.py writes (argv[1]: two such rows, written by FusedAdam._group_array), and the
 // argument structs that cross the boundary by value are trivially copyable.
 // Built and run by tests/test_kernels_h_cpp.py.
@@ -21,11 +21,12 @@ static int failures = 0;
     }                                                                         \
   } while (0)
 
-static_assert(sizeof(AdamGroup) == 32 && alignof(AdamGroup) == 4, "one float32 [8] row");
+static_assert(sizeof(AdamGroup) == 40 && alignof(AdamGroup) == 4 && ADAM_GROUP_COLS == 10, "one float32 [10] row");
 static_assert(offsetof(AdamGroup, lr) == 0 && offsetof(AdamGroup, beta1) == 4 && offsetof(AdamGroup, beta2) == 8 &&
                   offsetof(AdamGroup, eps) == 12 && offsetof(AdamGroup, weight_decay) == 16 && offsetof(AdamGroup, bc1) == 20 &&
-                  offsetof(AdamGroup, bc2_sqrt) == 24 && offsetof(AdamGroup, decoupled) == 28,
-              "columns 0..7 of the group table");
+                  offsetof(AdamGroup, bc2_sqrt) == 24 && offsetof(AdamGroup, decoupled) == 28 &&
+                  offsetof(AdamGroup, one_minus_beta1) == 32 && offsetof(AdamGroup, one_minus_beta2) == 36,
+              "columns 0..9 of the group table");
 static_assert(std::is_trivially_copyable<AdamGroup>::value && std::is_standard_layout<AdamGroup>::value, "AdamGroup");
 static_assert(std::is_trivially_copyable<DropSite>::value && std::is_standard_layout<DropSite>::value, "DropSite");
 static_assert(std::is_trivially_copyable<Fp8Copy>::value && std::is_standard_layout<Fp8Copy>::value, "Fp8Copy");
@@ -46,11 +47,11 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "usage: test_kernels_h <group table file>\n");
     return 2;
   }
-  float rows[16];
+  float rows[21];
   std::FILE* f = std::fopen(argv[1], "rb");
   CHECK(f != nullptr);
   if (f) {
-    CHECK(std::fread(rows, sizeof(float), 16, f) == 16);
+    CHECK(std::fread(rows, sizeof(float), 21, f) == 20);  // exactly two rows of 10
     std::fclose(f);
     AdamGroup g[2];
     std::memcpy(g, rows, sizeof(g));  // what bindings.cpp's reinterpret_cast reads
@@ -58,6 +59,7 @@ int main(int argc, char** argv) {
     CHECK(g[0].weight_decay == 0.0625f && g[0].bc1 == 0.625f && g[0].bc2_sqrt == 0.5f && g[0].decoupled == 1);
     CHECK(g[1].lr == 3.f && g[1].beta1 == 0.375f && g[1].beta2 == 0.75f && g[1].eps == 0.125f);
     CHECK(g[1].weight_decay == 0.f && g[1].bc1 == 0.625f && g[1].bc2_sqrt == 0.5f && g[1].decoupled == 0);
+    for (int i = 0; i < 2; ++i) CHECK(g[i].one_minus_beta1 == 0.625f && g[i].one_minus_beta2 == 0.25f);
   }
   if (failures) return 1;
   std::puts("all checks passed");

@@ -1,7 +1,7 @@
 """The host-kernel interface (csrc/kernels.h) is declared once and both sides use it.
 
 * ``test_kernels_h_under_host_compiler``: the header compiles under the plain host compiler, and
-  ``pvr::AdamGroup`` reads the float32 [G, 8] table that ``FusedAdam._group_array`` writes
+  ``pvr::AdamGroup`` reads the float32 [G, 10] table that ``FusedAdam._group_array`` writes
   (tests/cpp/test_kernels_h.cpp).
 * ``test_launchers_declared_once``: no ``extern "C"`` prototype of a ``pvr_*`` function outside the
   header (``pvr_src_hash`` in bindings.cpp, defined by the build, is the one exception), and every
@@ -30,7 +30,7 @@ def test_kernels_h_under_host_compiler(tmp_path):
     opt = FusedAdam([dict(params=[p0], lr=2.0, weight_decay=0.0625, decoupled_weight_decay=True),
                      dict(params=[p1], lr=3.0, weight_decay=0.0)], betas=(0.375, 0.75), eps=0.125)
     table = opt._group_array(1)
-    assert table.shape == (2, 8) and table.dtype.name == "float32"
+    assert table.shape == (2, 10) and table.dtype.name == "float32"
     table.tofile(str(tmp_path / "groups.bin"))
     exe = str(tmp_path / "test_kernels_h")
     cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__", f"-I{ROCM_INC}", SRC, "-o", exe]
