@@ -33,8 +33,11 @@ def build_parser():
     p.add_argument("--synthetic-test-len", type=int, default=128)
     p.add_argument("--epochs", type=int, default=5, help="total epochs (a --resume run trains the rest)")
     p.add_argument("--batch-size", type=int, default=32)
-    p.add_argument("--lr", type=float, default=1e-3)
-    p.add_argument("--weight-decay", type=float, default=0.03)
+    p.add_argument("--lr", type=float, default=1e-3, help="learning rate (LAMB recipes use about 3e-3)")
+    p.add_argument("--weight-decay", type=float, default=0.03, help="weight decay (LAMB recipes use 0.02-0.05)")
+    p.add_argument("--optimizer", choices=["adam", "adamw", "lamb"], default="adam",
+                   help="adam: coupled L2 decay (the reference recipe); adamw: decoupled decay; lamb: Adam's update scaled "
+                        "per parameter tensor by ||w|| / ||update|| (large batches; FusedLamb only)")
     p.add_argument("--warmup-frac", type=float, default=0.05)
     p.add_argument("--max-grad-norm", type=float, default=1.0)
     p.add_argument("--num-workers", type=int, default=4)
@@ -44,7 +47,8 @@ def build_parser():
     p.add_argument("--checkpoint-dir", default=None)
     p.add_argument("--resume", default=None)
     p.add_argument("--metrics", default=None, help="append per-epoch JSONL metrics here")
-    p.add_argument("--torch-optimizer", action="store_true", help="use torch.optim.Adam instead of FusedAdam")
+    p.add_argument("--torch-optimizer", action="store_true",
+                   help="use torch.optim.Adam / AdamW instead of FusedAdam (there is no torch LAMB)")
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--dtype", choices=["bf16", "fp8"], default="bf16",
                    help="fp8: the encoder GEMMs in fp8 with delayed scaling (ViT.enable_fp8; GPU fused path only)")
@@ -99,7 +103,7 @@ def main(argv=None) -> int:
     from ..data import DeviceInput, RandomResizedCropFlip, create_dataloaders, create_synthetic_dataloaders
     from ..data.transforms import default_vit_transform, uint8_transform
     from ..models import TinyVGG, vit
-    from ..optim import FusedAdam, ModelEma, param_groups_weight_decay, warmup_linear_decay
+    from ..optim import FusedAdam, FusedLamb, ModelEma, param_groups_weight_decay, warmup_linear_decay
     from ..parallel import DistributedDataParallel, init_distributed, is_dist
     from .. import _ext
     from ..utils import load_checkpoint, save_model, set_seeds
@@ -120,6 +124,8 @@ def main(argv=None) -> int:
         raise SystemExit("--patch-dropout does not combine with --dtype fp8")
     if not 0.0 <= args.patch_dropout < 1.0:
         raise SystemExit("--patch-dropout must be in [0, 1)")
+    if args.optimizer == "lamb" and args.torch_optimizer:
+        raise SystemExit("--optimizer lamb has no torch.optim counterpart: drop --torch-optimizer")
     if args.model_ema_warmup and args.model_ema is None:
         raise SystemExit("--model-ema-warmup needs --model-ema")
     if not args.device_preprocess and (args.augment != "none" or args.source_size is not None):
@@ -152,8 +158,12 @@ def main(argv=None) -> int:
             model.set_device_input(DeviceInput(augment=aug))
     model.to(device)
     groups = param_groups_weight_decay(model, args.weight_decay)
-    if args.torch_optimizer:
-        opt = torch.optim.Adam(groups, lr=args.lr, betas=(0.9, 0.999))
+    if args.optimizer == "lamb":
+        opt = FusedLamb(groups, lr=args.lr, betas=(0.9, 0.999))
+    elif args.torch_optimizer:
+        opt = (torch.optim.AdamW if args.optimizer == "adamw" else torch.optim.Adam)(groups, lr=args.lr, betas=(0.9, 0.999))
+    elif args.optimizer == "adamw":
+        opt = FusedAdam(groups, lr=args.lr, betas=(0.9, 0.999), decoupled_weight_decay=True)
     else:
         opt = FusedAdam(groups, lr=args.lr, betas=(0.9, 0.999))
     sched = warmup_linear_decay(opt, args.epochs * len(train_dl), args.warmup_frac)

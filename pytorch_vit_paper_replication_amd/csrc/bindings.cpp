@@ -840,6 +840,111 @@ void adam_t(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, 
         "adam_t");
 }
 
+// LAMB (lamb.hip): three launches over the flat buffers of adam. Segment tables: seg_group int32 [nseg]
+// (param group of each parameter tensor, -1 frozen), chunks int64 [nchunks][3] {flat start, elements,
+// segment}, seg_chunks int64 [nseg][2] {first chunk, chunks}; partial float32 [nchunks][2], trust
+// float32 [nseg][3] {||w||, ||u||, r}.
+void lamb_table(const torch::Tensor& t, const torch::Tensor& p, torch::ScalarType dt, int64_t cols, const char* who, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == p.device() && t.scalar_type() == dt && t.is_contiguous() && t.numel() < (int64_t(1) << 31) &&
+                  (cols == 0 ? t.dim() == 1 : (t.dim() == 2 && t.size(1) == cols)),
+              who, ": ", name, " must be a contiguous ", (dt == torch::kInt64 ? "int64" : dt == torch::kInt32 ? "int32" : "float32"),
+              cols == 0 ? " vector" : " table", " on the parameters' GPU", cols == 0 ? "" : " with ", cols == 0 ? "" : std::to_string(cols),
+              cols == 0 ? "" : " columns");
+}
+
+void lamb_moments(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, torch::Tensor chunks, torch::Tensor seg_group,
+                  torch::Tensor partial, torch::Tensor groups, c10::optional<torch::Tensor> clip, bool skip_nonfinite) {
+  const char* who = "lamb_moments";
+  TORCH_CHECK(p.is_cuda(), who, ": p must be a GPU tensor");
+  flat_f32(p, p, who, "p"); flat_f32(g, p, who, "g"); flat_f32(m, p, who, "m"); flat_f32(v, p, who, "v");
+  TORCH_CHECK(p.numel() == g.numel() && p.numel() == m.numel() && p.numel() == v.numel(), who, ": size mismatch");
+  TORCH_CHECK(p.numel() % 4 == 0, who, ": the flat buffers hold a multiple of 4 elements (the kernel works in float4), got ", p.numel());
+  const GroupTable gt = group_table(groups, p, who);
+  lamb_table(chunks, p, torch::kInt64, 3, who, "chunks");
+  lamb_table(seg_group, p, torch::kInt32, 0, who, "seg_group");
+  lamb_table(partial, p, torch::kFloat32, 2, who, "partial");
+  TORCH_CHECK(seg_group.numel() >= 1, who, ": seg_group must hold >= 1 segments");
+  TORCH_CHECK(partial.size(0) == chunks.size(0), who, ": partial must hold one row per chunk, got ", partial.size(0), " for ", chunks.size(0));
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(partial.data_ptr()) % 8 == 0, who, ": partial must be 8-byte aligned");
+  const float* pc = opt_clip(clip, p, who);
+  check(pvr_lamb_moments(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), p.numel(),
+                         chunks.data_ptr<int64_t>(), (int)chunks.size(0), seg_group.data_ptr<int>(), (int)seg_group.numel(),
+                         partial.data_ptr<float>(), gt.dev, gt.host, gt.n, pc, skip_nonfinite ? 1 : 0, stream()),
+        who);
+}
+
+void lamb_ratio(torch::Tensor partial, torch::Tensor seg_chunks, torch::Tensor seg_group, torch::Tensor trust, torch::Tensor groups,
+                c10::optional<torch::Tensor> clip, bool skip_nonfinite) {
+  const char* who = "lamb_ratio";
+  TORCH_CHECK(trust.is_cuda(), who, ": trust must be a GPU tensor");
+  lamb_table(trust, trust, torch::kFloat32, 3, who, "trust");
+  lamb_table(partial, trust, torch::kFloat32, 2, who, "partial");
+  lamb_table(seg_chunks, trust, torch::kInt64, 2, who, "seg_chunks");
+  lamb_table(seg_group, trust, torch::kInt32, 0, who, "seg_group");
+  TORCH_CHECK(seg_group.numel() >= 1 && seg_chunks.size(0) == seg_group.numel() && trust.size(0) == seg_group.numel(), who,
+              ": seg_chunks, seg_group and trust must hold the same number (>= 1) of segments");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(partial.data_ptr()) % 8 == 0, who, ": partial must be 8-byte aligned");
+  const GroupTable gt = group_table(groups, trust, who);
+  const float* pc = opt_clip(clip, trust, who);
+  check(pvr_lamb_ratio(partial.data_ptr<float>(), (int)partial.size(0), seg_chunks.data_ptr<int64_t>(), seg_group.data_ptr<int>(),
+                       (int)seg_group.numel(), trust.data_ptr<float>(), gt.dev, gt.host, gt.n, pc, skip_nonfinite ? 1 : 0, stream()),
+        who);
+}
+
+// The segment-table form (seg_start, seg_group; shadow optional) or, with shadow_t / tmeta [nmat][7] /
+// ntiles / fmeta [nflat][5] / flat4, the tile form that also writes W^T (adam_t's tables with the
+// segment index appended to every row).
+void lamb_update(torch::Tensor p, torch::Tensor m, torch::Tensor v, c10::optional<torch::Tensor> shadow, torch::Tensor trust,
+                 torch::Tensor groups, c10::optional<torch::Tensor> clip, bool skip_nonfinite, c10::optional<torch::Tensor> seg_start,
+                 c10::optional<torch::Tensor> seg_group, c10::optional<torch::Tensor> shadow_t, c10::optional<torch::Tensor> tmeta,
+                 int64_t ntiles, c10::optional<torch::Tensor> fmeta, int64_t flat4, c10::optional<torch::Tensor> ema,
+                 c10::optional<torch::Tensor> ema_pair) {
+  const char* who = "lamb_update";
+  TORCH_CHECK(p.is_cuda(), who, ": p must be a GPU tensor");
+  flat_f32(p, p, who, "p"); flat_f32(m, p, who, "m"); flat_f32(v, p, who, "v");
+  TORCH_CHECK(p.numel() == m.numel() && p.numel() == v.numel(), who, ": size mismatch");
+  TORCH_CHECK(p.numel() % 4 == 0, who, ": the flat buffers hold a multiple of 4 elements (the kernel works in float4), got ", p.numel());
+  const GroupTable gt = group_table(groups, p, who);
+  lamb_table(trust, p, torch::kFloat32, 3, who, "trust");
+  TORCH_CHECK(trust.size(0) >= 1, who, ": trust must hold >= 1 segments");
+  uint16_t* sh = nullptr;
+  if (shadow.has_value() && shadow->defined()) {
+    flat_bf16(*shadow, p, 8, who, "shadow");
+    TORCH_CHECK(shadow->numel() == p.numel(), who, ": shadow must hold the parameters' ", p.numel(), " elements, got ", shadow->numel());
+    sh = reinterpret_cast<uint16_t*>(shadow->data_ptr());
+  }
+  const bool tiles = tmeta.has_value() && tmeta->defined();
+  const int64_t* ss = nullptr; const int* sg = nullptr; int nseg = 0;
+  uint16_t* sht = nullptr; const int64_t* tm = nullptr; const int64_t* fm = nullptr; int nmat = 0, nflat = 0;
+  if (tiles) {
+    TORCH_CHECK(sh != nullptr && shadow_t.has_value() && shadow_t->defined() && fmeta.has_value() && fmeta->defined(), who,
+                ": the tile form needs shadow, shadow_t, tmeta and fmeta");
+    flat_bf16(*shadow_t, p, 16, who, "shadow_t");
+    lamb_table(*tmeta, p, torch::kInt64, 7, who, "tmeta");
+    lamb_table(*fmeta, p, torch::kInt64, 5, who, "fmeta");
+    TORCH_CHECK(tmeta->size(0) >= 1 && fmeta->size(0) >= 1, who, ": tmeta and fmeta hold >= 1 rows");
+    TORCH_CHECK(ntiles >= 1 && ntiles < (int64_t(1) << 31) && flat4 >= 0, who, ": ntiles >= 1 and flat4 >= 0");
+    sht = reinterpret_cast<uint16_t*>(shadow_t->data_ptr());
+    tm = tmeta->data_ptr<int64_t>(); nmat = (int)tmeta->size(0);
+    fm = fmeta->data_ptr<int64_t>(); nflat = (int)fmeta->size(0);
+  } else {
+    TORCH_CHECK(seg_start.has_value() && seg_start->defined() && seg_group.has_value() && seg_group->defined(), who,
+                ": the segment-table form needs seg_start and seg_group");
+    lamb_table(*seg_start, p, torch::kInt64, 0, who, "seg_start");
+    lamb_table(*seg_group, p, torch::kInt32, 0, who, "seg_group");
+    TORCH_CHECK(seg_start->numel() >= 1 && seg_start->numel() == seg_group->numel() && trust.size(0) == seg_start->numel(), who,
+                ": seg_start, seg_group and trust must hold the same number (>= 1) of segments");
+    TORCH_CHECK(ntiles == 0, who, ": ntiles without tmeta");
+    ss = seg_start->data_ptr<int64_t>(); sg = seg_group->data_ptr<int>(); nseg = (int)seg_start->numel();
+  }
+  const float* pc = opt_clip(clip, p, who);
+  const pvr::AdamEma ea = ema_args(p, ema, ema_pair, who);
+  check(pvr_lamb_update(p.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), sh, sht, p.numel(), ss, sg, nseg, tm, nmat,
+                        (int)ntiles, fm, nflat, flat4, trust.data_ptr<float>(), gt.dev, gt.host, gt.n, pc, skip_nonfinite ? 1 : 0, ea,
+                        stream()),
+        who);
+}
+
 // Classifier head forward: LayerNorm of each image's CLS row (token 0 of tokens [B*N][D] bf16) and
 // logits = LN(x) . W^T + bias in fp32. Returns {logits [B][C], xhat [B][D], rstd [B]} (the latter two
 // saved for head_bwd).
@@ -1392,6 +1497,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adam_t", &adam_t, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("shadow"), py::arg("shadow_t"),
         py::arg("tmeta"), py::arg("ntiles"), py::arg("fmeta"), py::arg("flat4"), py::arg("groups"), py::arg("clip"),
         py::arg("skip_nonfinite"), py::arg("ema") = py::none(), py::arg("ema_pair") = py::none());
+  m.def("lamb_chunk", []() { return (int)pvr::LAMB_CHUNK; });
+  m.def("lamb_moments", &lamb_moments, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("chunks"), py::arg("seg_group"),
+        py::arg("partial"), py::arg("groups"), py::arg("clip"), py::arg("skip_nonfinite"));
+  m.def("lamb_ratio", &lamb_ratio, py::arg("partial"), py::arg("seg_chunks"), py::arg("seg_group"), py::arg("trust"), py::arg("groups"),
+        py::arg("clip"), py::arg("skip_nonfinite"));
+  m.def("lamb_update", &lamb_update, py::arg("p"), py::arg("m"), py::arg("v"), py::arg("shadow"), py::arg("trust"), py::arg("groups"),
+        py::arg("clip"), py::arg("skip_nonfinite"), py::arg("seg_start") = py::none(), py::arg("seg_group") = py::none(),
+        py::arg("shadow_t") = py::none(), py::arg("tmeta") = py::none(), py::arg("ntiles") = 0, py::arg("fmeta") = py::none(),
+        py::arg("flat4") = 0, py::arg("ema") = py::none(), py::arg("ema_pair") = py::none());
   m.def("scale_by_clip", &scale_by_clip);
   m.def("head_fwd", &head_fwd);
   m.def("head_bwd", &head_bwd, py::arg("dlogits"), py::arg("xhat"), py::arg("rstd"), py::arg("gamma"), py::arg("beta"), py::arg("W"),

@@ -33,6 +33,13 @@ struct AdamEma {
   float* buf = nullptr; const float* pair = nullptr; float decay = 0.f, one_minus_decay = 1.f;
 };
 
+// LAMB (lamb.hip) reads the same table. Its rows keep `decoupled` bit 0 clear and carry the group's
+// always_adapt option in bit 1: a group takes the trust ratio ||w|| / ||u|| when its weight_decay is
+// non-zero or this bit is set, and plain Adam steps otherwise. The Adam kernels never see such a row.
+constexpr int LAMB_ALWAYS_ADAPT = 2;
+// Elements of one chunk of the LAMB norm pass: one workgroup, 4 float4 per thread
+constexpr int LAMB_CHUNK = 4096;
+
 // A dropout site: the element's 16-bit hash of (*seed + offset) is kept iff >= thr = round(p * 65536);
 // kept values scale by 65536 / (65536 - thr). seed null: no dropout.
 struct DropSite {
@@ -233,6 +240,31 @@ hipError_t pvr_adam_t(float* p, const float* g, float* m, float* v, uint16_t* sh
                       int nmat, int ntiles, const int64_t* fmeta, int nflat, int64_t flat4, const pvr::AdamGroup* groups,
                       const pvr::AdamGroup* host_groups, int ngroups, const float* clip, int skip_nonfinite, pvr::AdamEma ema,
                       hipStream_t s);
+
+// ---- lamb.hip
+// LAMB on the flat buffers of pvr_adam, three launches. Segment i is one parameter tensor; seg_group
+// int32 [nseg] its param group (-1 frozen). groups / host_groups / clip / skip_nonfinite as in pvr_adam;
+// all three return at once on a skipped non-finite step.
+// 1: moments. chunks int64 [nchunks][3] {flat start, elements (multiple of 4, <= LAMB_CHUNK), segment};
+// a chunk lies inside one trainable segment. Writes m, v and partial f32 [nchunks][2] = the chunk's
+// {sum p^2, sum u^2}, u = (m / bc1) / (sqrt(v) / bc2_sqrt + eps) + weight_decay * p. n: elements of the buffers.
+hipError_t pvr_lamb_moments(const float* p, const float* g, float* m, float* v, int64_t n, const int64_t* chunks, int nchunks,
+                            const int* seg_group, int nseg, float* partial, const pvr::AdamGroup* groups,
+                            const pvr::AdamGroup* host_groups, int ngroups, const float* clip, int skip_nonfinite, hipStream_t s);
+// 2: trust f32 [nseg][3] = {||w||, ||u||, r} per trainable segment from its chunks' partials, summed in
+// double in a fixed order. seg_chunks int64 [nseg][2] {first chunk, chunks}; rows of frozen segments stay.
+hipError_t pvr_lamb_ratio(const float* partial, int nchunks, const int64_t* seg_chunks, const int* seg_group, int nseg, float* trust,
+                          const pvr::AdamGroup* groups, const pvr::AdamGroup* host_groups, int ngroups, const float* clip,
+                          int skip_nonfinite, hipStream_t s);
+// 3: p -= lr * trust[seg].r * u with u recomputed from the new m, v; bf16 shadow, W^T and the model EMA
+// as pvr_adam / pvr_adam_t write them. ntiles > 0: the tile form, tmeta int64 [nmat][7] and fmeta int64
+// [nflat][5] = pvr_adam_t's rows with the segment index appended. ntiles == 0: the segment-table form
+// over n elements (seg_start int64 [nseg]; shadow optional).
+hipError_t pvr_lamb_update(float* p, const float* m, const float* v, uint16_t* shadow, uint16_t* shadow_t, int64_t n,
+                           const int64_t* seg_start, const int* seg_group, int nseg, const int64_t* tmeta, int nmat, int ntiles,
+                           const int64_t* fmeta, int nflat, int64_t flat4, const float* trust, const pvr::AdamGroup* groups,
+                           const pvr::AdamGroup* host_groups, int ngroups, const float* clip, int skip_nonfinite, pvr::AdamEma ema,
+                           hipStream_t s);
 
 // ---- fp8.hip
 hipError_t pvr_fp8_quant(const uint16_t* x, int64_t ldx, uint8_t* y, int64_t ldy, int64_t rows, int cols, const float* qscale,

@@ -1,6 +1,7 @@
 """Optimizers and schedules (reference recipe: MAIN.ipynb:2792-2960)."""
 from .adam import FusedAdam
 from .ema import ModelEma
+from .lamb import FusedLamb
 from .schedule import param_groups_weight_decay, warmup_decay_steps, warmup_linear_decay
 
-__all__ = ["FusedAdam", "ModelEma", "param_groups_weight_decay", "warmup_decay_steps", "warmup_linear_decay"]
+__all__ = ["FusedAdam", "FusedLamb", "ModelEma", "param_groups_weight_decay", "warmup_decay_steps", "warmup_linear_decay"]

@@ -129,9 +129,10 @@ class FusedAdam(torch.optim.Optimizer):
             for p in g["params"]:
                 group_of[id(p)] = gi
         meta = tmeta_dev.cpu().tolist()
+        extra = self._table_row_extra(store)  # columns a subclass's kernels read behind these
         trows, tiles = [], 0
         for p, (soff, toff, R, C, _) in zip(tparams, meta):
-            trows.append([soff, toff, R, C, tiles, group_of.get(id(p), -1) if p.requires_grad else -1])
+            trows.append([soff, toff, R, C, tiles, group_of.get(id(p), -1) if p.requires_grad else -1] + extra.get(id(p), []))
             tiles += (R // 64) * (C // 64)
         tids = {id(p) for p in tparams}
         frows, f4 = [], 0
@@ -139,13 +140,17 @@ class FusedAdam(torch.optim.Optimizer):
             if id(p) in tids:
                 continue
             n = (p.numel() + 3) // 4 * 4  # the store pads every segment (zeros stay zero)
-            frows.append([off, n, group_of.get(id(p), -1) if p.requires_grad else -1, f4])
+            frows.append([off, n, group_of.get(id(p), -1) if p.requires_grad else -1, f4] + extra.get(id(p), []))
             f4 += n // 4
         dev = store.device
         self._ttables = (torch.tensor(trows, dtype=torch.int64, device=dev), tiles,
                          torch.tensor(frows, dtype=torch.int64, device=dev), f4)
         self._tmeta_key = key
         return self._ttables
+
+    def _table_row_extra(self, store) -> dict:
+        """Further columns per parameter (by id) for the rows of ``_transposed_tables``; none for Adam."""
+        return {}
 
     def _group_array(self, step: int, arr: Optional[np.ndarray] = None) -> np.ndarray:
         """The kernels' group table (csrc/kernels.h AdamGroup), float32 [G, GROUP_COLS]. 1 - beta is
@@ -165,8 +170,12 @@ class FusedAdam(torch.optim.Optimizer):
             arr[i, 6] = math.sqrt(1.0 - b2 ** step)
             arr[i, 8] = 1.0 - b1
             arr[i, 9] = 1.0 - b2
-        arr.view(np.int32)[:, 7] = [int(bool(g["decoupled_weight_decay"])) for g in self.param_groups]
+        arr.view(np.int32)[:, 7] = [self._group_flags(g) for g in self.param_groups]
         return arr
+
+    def _group_flags(self, g) -> int:
+        """Word 7 of a group's table row (an int)."""
+        return int(bool(g["decoupled_weight_decay"]))
 
     def _group_table(self, step: int, device) -> torch.Tensor:
         if not self._graph:
@@ -279,17 +288,7 @@ class FusedAdam(torch.optim.Optimizer):
                 # captured steps read the pair graph_prepare() uploaded; eager ones take it by value
                 pair = self._ema_pair_dev if self._graph else torch.from_numpy(np.array(ema.next_pair(), dtype=np.float32))
                 ema_kw = dict(ema=ema_buf, ema_pair=pair)
-            tt = self._transposed_tables(store)  # Adam also writes the bf16 W^T shadow when it can
-            if tt is not None and tt[3] > 0:
-                # master, m, v, bf16 shadow and the dgrad GEMMs' W^T shadow in one pass
-                store.ensure_transposed()  # only if something else changed the weights since
-                _ext.ext().adam_t(store.flat, store.grad_flat, m, v, store.shadow, store.shadow_t, tt[0], tt[1], tt[2], tt[3],
-                                  table, clip if use_clip else None, self.skip_nonfinite, **ema_kw)
-                store.mark_shadow_fresh(transposed=True)
-            else:
-                _ext.ext().adam(store.flat, store.grad_flat, m, v, store.shadow, seg_start, seg_group, table,
-                                clip if use_clip else None, self.skip_nonfinite, **ema_kw)
-                store.mark_shadow_fresh()
+            self._fused_update(fz, table, clip if use_clip else None, ema_kw)
             self._pending_clip = False
             if ema is not None and ema_buf is None:
                 ema.update()  # the EMA's model is not this store's: torch ops
@@ -297,6 +296,28 @@ class FusedAdam(torch.optim.Optimizer):
         # ---------------- reference math (torch.optim.Adam, single-tensor, maximize=False)
         if clip_norm is not None:
             self.clip_grad_norm_(clip_norm)
+        self._torch_update()
+        if self._ema is not None:
+            self._ema.update()
+        return loss
+
+    def _fused_update(self, fz, table, clip, ema_kw) -> None:
+        """The update launch(es) of a fused step, behind the norm kernels."""
+        store, m, v, seg_start, seg_group = fz[:5]
+        tt = self._transposed_tables(store)  # Adam also writes the bf16 W^T shadow when it can
+        if tt is not None and tt[3] > 0:
+            # master, m, v, bf16 shadow and the dgrad GEMMs' W^T shadow in one pass
+            store.ensure_transposed()  # only if something else changed the weights since
+            _ext.ext().adam_t(store.flat, store.grad_flat, m, v, store.shadow, store.shadow_t, tt[0], tt[1], tt[2], tt[3],
+                              table, clip, self.skip_nonfinite, **ema_kw)
+            store.mark_shadow_fresh(transposed=True)
+        else:
+            _ext.ext().adam(store.flat, store.grad_flat, m, v, store.shadow, seg_start, seg_group, table,
+                            clip, self.skip_nonfinite, **ema_kw)
+            store.mark_shadow_fresh()
+
+    def _torch_update(self) -> None:
+        """The reference math (torch.optim.Adam, single-tensor, maximize=False) off the fused path."""
         for g in self.param_groups:
             b1, b2 = g["betas"]
             lr, eps, wd = g["lr"], g["eps"], g["weight_decay"]
@@ -322,9 +343,6 @@ class FusedAdam(torch.optim.Optimizer):
                 step_size = lr / bc1
                 denom = (st["exp_avg_sq"].sqrt() / math.sqrt(bc2)).add_(eps)
                 p.addcdiv_(st["exp_avg"], denom, value=-step_size)
-        if self._ema is not None:
-            self._ema.update()
-        return loss
 
     def state_dict(self):
         if self._fused is not None:  # per-tensor step counters are materialised lazily
