@@ -78,6 +78,11 @@ def build_parser():
     p.add_argument("--mix-prob", type=float, default=1.0, help="probability that a batch is mixed")
     p.add_argument("--mix-switch-prob", type=float, default=0.5, help="with both: probability of CutMix over mixup")
     p.add_argument("--label-smoothing", type=float, default=0.0, metavar="E", help="label smoothing of the loss (0: off)")
+    p.add_argument("--random-erasing", type=float, default=0.0, metavar="P",
+                   help="random erasing: erase one random box of each training image with this probability (0: off; "
+                        "the DeiT recipe uses 0.25)")
+    p.add_argument("--random-erasing-mode", choices=["pixel", "const"], default="pixel",
+                   help="with --random-erasing: fill the box with per-pixel standard normal noise, or with the mean colour")
     p.add_argument("--model-ema", type=float, nargs="?", const=0.9999, default=None, metavar="DECAY",
                    help="keep an exponential moving average of the weights (bare flag: 0.9999): it is what the test "
                         "pass evaluates, checkpoints carry it and <name>_ema.pth is written beside the model")
@@ -96,6 +101,17 @@ def build_batch_mix(args, rank: int = 0):
     gen = torch.Generator().manual_seed(args.seed * 1_000_003 + 7919 + rank)
     return BatchMix(mixup_alpha=args.mixup, cutmix_alpha=args.cutmix, prob=args.mix_prob, switch_prob=args.mix_switch_prob,
                     label_smoothing=args.label_smoothing, generator=gen)
+
+
+def build_random_erasing(args, rank: int = 0):
+    """The :class:`~..data.random_erasing.RandomErasing` of ``--random-erasing`` (None when it is 0), its generator
+    seeded from ``--seed`` per rank."""
+    if args.random_erasing <= 0:
+        return None
+    from ..data.random_erasing import RandomErasing
+
+    gen = torch.Generator().manual_seed(args.seed * 1_000_003 + 15485863 + rank)
+    return RandomErasing(prob=args.random_erasing, mode=args.random_erasing_mode, generator=gen)
 
 
 def main(argv=None) -> int:
@@ -124,6 +140,8 @@ def main(argv=None) -> int:
         raise SystemExit("--patch-dropout does not combine with --dtype fp8")
     if not 0.0 <= args.patch_dropout < 1.0:
         raise SystemExit("--patch-dropout must be in [0, 1)")
+    if not 0.0 <= args.random_erasing <= 1.0:
+        raise SystemExit("--random-erasing must be in [0, 1]")
     if args.optimizer == "lamb" and args.torch_optimizer:
         raise SystemExit("--optimizer lamb has no torch.optim counterpart: drop --torch-optimizer")
     if args.model_ema_warmup and args.model_ema is None:
@@ -193,7 +211,7 @@ def main(argv=None) -> int:
                      loss_fn=torch.nn.CrossEntropyLoss(label_smoothing=args.label_smoothing), lr_scheduler=sched,
                      epochs=args.epochs, device=device, max_grad_norm=args.max_grad_norm, checkpoint_dir=args.checkpoint_dir,
                      metrics_path=args.metrics, start_epoch=start_epoch, results=results,
-                     batch_mix=build_batch_mix(args, rank), model_ema=ema)
+                     batch_mix=build_batch_mix(args, rank), model_ema=ema, random_erasing=build_random_erasing(args, rank))
     name = args.save_name or f"{args.model}_{args.epochs}_epochs.pth"
     save_model(model, args.save_dir, name)
     if ema is not None:

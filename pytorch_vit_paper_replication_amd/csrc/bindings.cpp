@@ -496,6 +496,72 @@ const pvr::MixRow* mix_rows(const c10::optional<torch::Tensor>& mix, const c10::
   return reinterpret_cast<const pvr::MixRow*>(mix->data_ptr());
 }
 
+// A random-erasing plan for the patchify kernels (csrc/kernels.h EraseRow / EraseArgs): `erase` int32 [B, 4]
+// on the image's device, validated here on the host like a mix plan (`host`: the CPU tensor it was
+// uploaded from, data/random_erasing.py ErasePlan; without it the device tensor is read back, which
+// synchronises), before any kernel runs. mode: "const" (value: one float per channel, or one for all) or
+// "pixel" (seed: the step's int64 device counter, offset: the site's offset).
+pvr::EraseArgs erase_args(const c10::optional<torch::Tensor>& erase, const c10::optional<torch::Tensor>& host, const std::string& mode,
+                          const std::vector<double>& value, const c10::optional<torch::Tensor>& seed, int64_t offset, int64_t B,
+                          int64_t C, int64_t H, int64_t W, const torch::Tensor& img, const char* what) {
+  pvr::EraseArgs e;
+  if (!erase.has_value() || !erase->defined()) {
+    TORCH_CHECK(!host.has_value() || !host->defined(), what, ": erase_host without erase");
+    return e;
+  }
+  TORCH_CHECK(erase->is_cuda() && erase->device() == img.device(), what, ": erase must be on the image's device");
+  TORCH_CHECK(erase->scalar_type() == torch::kInt32 && erase->dim() == 2 && erase->size(0) == B && erase->size(1) == 4 &&
+                  erase->is_contiguous(),
+              what, ": erase must be contiguous int32 [", B, ", 4]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(erase->data_ptr()) % 16 == 0, what, ": erase must be 16-byte aligned");
+  TORCH_CHECK(C >= 1 && C <= 4, what, ": erasing takes 1..4 channels, got ", C);
+  TORCH_CHECK(B * C * H * W < (int64_t(1) << 62), what, ": erase: too many elements");
+  torch::Tensor h;
+  if (host.has_value() && host->defined()) {
+    TORCH_CHECK(!host->is_cuda() && host->scalar_type() == torch::kInt32 && host->dim() == 2 && host->size(0) == B &&
+                    host->size(1) == 4 && host->is_contiguous(),
+                what, ": erase_host must be a contiguous CPU int32 [", B, ", 4] tensor");
+    h = *host;
+  } else {
+    h = erase->cpu();
+  }
+  const auto* rows = reinterpret_cast<const pvr::EraseRow*>(h.data_ptr());
+  for (int64_t b = 0; b < B; ++b) {
+    const pvr::EraseRow& r = rows[b];
+    TORCH_CHECK(r.x0 >= 0 && r.x0 <= r.x1 && r.x1 <= W && r.y0 >= 0 && r.y0 <= r.y1 && r.y1 <= H, what, ": erase row ", b,
+                " has box (", r.x0, ", ", r.y0, ", ", r.x1, ", ", r.y1, ") outside the ", H, "x", W, " image");
+  }
+  if (mode == "pixel") {
+    TORCH_CHECK(seed.has_value() && seed->defined(), what, ": erase mode \"pixel\" needs erase_seed, the int64 device counter");
+    TORCH_CHECK(seed->is_cuda() && seed->device() == img.device() && seed->scalar_type() == torch::kInt64 && seed->numel() >= 1,
+                what, ": erase_seed must be an int64 tensor on the image's device");
+    e.mode = pvr::ERASE_PIXEL;
+    e.seed = reinterpret_cast<const uint64_t*>(seed->data_ptr());
+    e.offset = (uint64_t)offset;
+  } else {
+    TORCH_CHECK(mode == "const", what, ": erase_mode must be \"pixel\" or \"const\", got \"", mode, "\"");
+    TORCH_CHECK(value.size() == 1 || (int64_t)value.size() == C, what, ": erase_value needs one value, or one per channel");
+    for (int64_t c = 0; c < C; ++c) e.value[c] = (float)value[value.size() == 1 ? 0 : c];
+  }
+  e.rows = reinterpret_cast<const pvr::EraseRow*>(erase->data_ptr());
+  return e;
+}
+
+// The "pixel" fill of random erasing for every element of a [B, C, H, W] model image at site `site_offset`
+// of the counter value *seed (csrc/elementwise.hip erase_normal, the function the patchify kernels call):
+// diagnostics, and the tests' and the reference path's replay of the kernels' noise.
+torch::Tensor erase_noise(torch::Tensor seed, int64_t site_offset, int64_t B, int64_t C, int64_t H, int64_t W) {
+  TORCH_CHECK(seed.is_cuda() && seed.scalar_type() == torch::kInt64 && seed.numel() >= 1,
+              "erase_noise: seed must be an int64 tensor on the GPU");
+  TORCH_CHECK(B >= 0 && C >= 0 && H >= 0 && W >= 0 && B < (1ll << 31) && C < (1ll << 31) && H < (1ll << 31) && W < (1ll << 31),
+              "erase_noise: bad shape");
+  auto out = torch::empty({B, C, H, W}, seed.options().dtype(torch::kFloat32));
+  check(pvr_erase_noise(reinterpret_cast<const uint64_t*>(seed.data_ptr()), (uint64_t)site_offset, out.data_ptr<float>(), out.numel(),
+                        stream()),
+        "erase_noise");
+  return out;
+}
+
 // Patch dropout's keep table (csrc/elementwise.hip patch_keep_kernel): (keep int32 [B, n_keep], inv int32
 // [B, n_p]) of the site `site_offset` at the counter value *seed. The fused forward's draw, and the
 // tests' and the reference path's replay of it.
@@ -541,16 +607,20 @@ torch::Tensor pos_gather(torch::Tensor pos, torch::Tensor keep) {
 }
 
 void im2col(torch::Tensor img, torch::Tensor out, int64_t P, int64_t Kp, c10::optional<torch::Tensor> mix,
-            c10::optional<torch::Tensor> mix_host, c10::optional<torch::Tensor> keep) {
+            c10::optional<torch::Tensor> mix_host, c10::optional<torch::Tensor> keep, c10::optional<torch::Tensor> erase,
+            c10::optional<torch::Tensor> erase_host, std::string erase_mode, std::vector<double> erase_value,
+            c10::optional<torch::Tensor> erase_seed, int64_t erase_offset) {
   TORCH_CHECK(img.is_contiguous() && img.dim() == 4, "im2col: img must be contiguous NCHW");
   const pvr::MixRow* mp = mix_rows(mix, mix_host, img.size(0), img.size(2), img.size(3), img, "im2col");
+  const pvr::EraseArgs ea = erase_args(erase, erase_host, erase_mode, erase_value, erase_seed, erase_offset, img.size(0), img.size(1),
+                                       img.size(2), img.size(3), img, "im2col");
   int64_t n_keep = 0;
   const int* kp = nullptr;
   if (keep.has_value() && keep->defined()) {  // (the plain call keeps its checks, as with a plan below)
     TORCH_CHECK(P > 0, "im2col: patch size");
     kp = keep_rows(keep, img.size(0), (img.size(2) / P) * (img.size(3) / P), img, &n_keep, "im2col");
   }
-  if (mp || kp) {  // the plain call keeps its checks; a plan adds those that keep the second read in bounds
+  if (mp || kp || ea.rows) {  // the plain call keeps its checks; a plan adds those that keep the second read in bounds
     const int64_t rows = P > 0 ? img.size(0) * (kp ? n_keep : (img.size(2) / P) * (img.size(3) / P)) : -1;
     TORCH_CHECK(img.is_cuda() && P > 0 && img.size(2) % P == 0 && img.size(3) % P == 0 && Kp % 8 == 0 &&
                     Kp >= img.size(1) * P * P,
@@ -560,7 +630,7 @@ void im2col(torch::Tensor img, torch::Tensor out, int64_t P, int64_t Kp, c10::op
                 "im2col: out must be contiguous bf16 [", rows, ", ", Kp, "] on the image's device");
   }
   check(pvr_im2col(f32(img, "img"), bf_mut(out, "out"), (int)img.size(0), (int)img.size(1), (int)img.size(2), (int)img.size(3),
-                   (int)P, (int)Kp, mp, kp, (int)n_keep, stream()),
+                   (int)P, (int)Kp, mp, kp, (int)n_keep, ea, stream()),
         "im2col");
 }
 
@@ -570,7 +640,9 @@ void im2col(torch::Tensor img, torch::Tensor out, int64_t P, int64_t Kp, c10::op
 // the 8-byte-load path ran, 0 for the per-element path (decided here from data_ptr and strides).
 int64_t im2col_u8(torch::Tensor img, torch::Tensor out, std::vector<double> mean, std::vector<double> stdv,
                   c10::optional<torch::Tensor> geom, int64_t H, int64_t W, int64_t P, int64_t Kp, c10::optional<torch::Tensor> mix,
-                  c10::optional<torch::Tensor> mix_host, c10::optional<torch::Tensor> keep) {
+                  c10::optional<torch::Tensor> mix_host, c10::optional<torch::Tensor> keep, c10::optional<torch::Tensor> erase,
+                  c10::optional<torch::Tensor> erase_host, std::string erase_mode, std::vector<double> erase_value,
+                  c10::optional<torch::Tensor> erase_seed, int64_t erase_offset) {
   TORCH_CHECK(img.is_cuda() && img.scalar_type() == torch::kUInt8, "im2col_u8: img must be a uint8 GPU tensor, got ",
               img.scalar_type(), " on ", img.device());
   TORCH_CHECK(img.dim() == 4, "im2col_u8: img must be [B, C, Hs, Ws], got ", img.dim(), " dims");
@@ -601,6 +673,7 @@ int64_t im2col_u8(torch::Tensor img, torch::Tensor out, std::vector<double> mean
     TORCH_CHECK(Hs == H && Ws == W, "im2col_u8: a ", Hs, "x", Ws, " source needs geom to produce ", H, "x", W);
   }
   const pvr::MixRow* mp = mix_rows(mix, mix_host, B, H, W, img, "im2col_u8");
+  const pvr::EraseArgs ea = erase_args(erase, erase_host, erase_mode, erase_value, erase_seed, erase_offset, B, C, H, W, img, "im2col_u8");
   const int64_t sb = img.stride(0), sc = img.stride(1), sy = img.stride(2), sx = img.stride(3);
   TORCH_CHECK(sb >= 0 && sc >= 0 && sy >= 0 && sx >= 0, "im2col_u8: negative strides");
   const uint8_t* ip = img.data_ptr<uint8_t>();
@@ -611,7 +684,7 @@ int64_t im2col_u8(torch::Tensor img, torch::Tensor out, std::vector<double> mean
     sd[c] = (float)stdv[c];
   }
   check(pvr_im2col_u8(ip, sb, sc, sy, sx, m, sd, gp, bf_mut(out, "out"), (int)B, (int)C, (int)Hs, (int)Ws, (int)H, (int)W, (int)P,
-                      (int)Kp, vec, mp, kp, (int)n_keep, stream()),
+                      (int)Kp, vec, mp, kp, (int)n_keep, ea, stream()),
         "im2col_u8");
   return vec;
 }
@@ -1475,10 +1548,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q_amax") = py::none(), py::arg("q_fmt") = 1, py::arg("row_mul") = 1, py::arg("dp_seed") = py::none(),
         py::arg("dp_offset") = 0, py::arg("dp_p") = 0.0, py::arg("dp_rows") = 1);
   m.def("im2col", &im2col, py::arg("img"), py::arg("out"), py::arg("P"), py::arg("Kp"), py::arg("mix") = py::none(),
-        py::arg("mix_host") = py::none(), py::arg("keep") = py::none());
+        py::arg("mix_host") = py::none(), py::arg("keep") = py::none(), py::arg("erase") = py::none(),
+        py::arg("erase_host") = py::none(), py::arg("erase_mode") = "const", py::arg("erase_value") = std::vector<double>{0.0},
+        py::arg("erase_seed") = py::none(), py::arg("erase_offset") = 0);
   m.def("im2col_u8", &im2col_u8, py::arg("img"), py::arg("out"), py::arg("mean"), py::arg("std"), py::arg("geom"), py::arg("H"),
         py::arg("W"), py::arg("P"), py::arg("Kp"), py::arg("mix") = py::none(), py::arg("mix_host") = py::none(),
-        py::arg("keep") = py::none());
+        py::arg("keep") = py::none(), py::arg("erase") = py::none(), py::arg("erase_host") = py::none(),
+        py::arg("erase_mode") = "const", py::arg("erase_value") = std::vector<double>{0.0}, py::arg("erase_seed") = py::none(),
+        py::arg("erase_offset") = 0);
+  m.def("erase_noise", &erase_noise, py::arg("seed"), py::arg("site_offset"), py::arg("B"), py::arg("C"), py::arg("H"), py::arg("W"));
   m.def("patch_keep_table", &patch_keep_table, py::arg("seed"), py::arg("site_offset"), py::arg("B"), py::arg("n_p"), py::arg("n_keep"));
   m.def("pos_gather", &pos_gather, py::arg("pos"), py::arg("keep"));
   m.def("cls_rows", &cls_rows);

@@ -4,7 +4,8 @@
 //   * patch embedding: im2col gather (fp32 image -> bf16 patch rows), CLS rows, and the backward
 //     reduction of the embedding-dropout / position-embedding / CLS gradients;
 //   * patch dropout: the per-sample keep table (ranks of counter-hash keys), the gathered position
-//     addend, and the KEEP instantiations of the patchify kernels and of the backward's first pass.
+//     addend, and the KEEP instantiations of the patchify kernels and of the backward's first pass;
+//   * random erasing: the ERASE instantiations of the patchify kernels and the fill's noise as a kernel.
 #include "common.h"
 #include "kernels.h"
 
@@ -231,6 +232,50 @@ PVR_DEV MixRow mix_row(const MixRow* __restrict__ mix, int b, int B) {
   return r;
 }
 
+// a[c] of a by-value kernel argument without a divergent index into the argument segment
+PVR_DEV float pick4(const float (&a)[4], int c) { return c == 0 ? a[0] : c == 1 ? a[1] : c == 2 ? a[2] : a[3]; }
+
+// Random erasing (EraseRow / EraseArgs in kernels.h). The "pixel" fill of element e at site seed sd: a
+// standard normal by Box-Muller from two hashes of the dropout counter. u1 = ((h1 >> 8) + 1) * 2^-24 lies
+// in (0, 1] and u2 = (h2 >> 8) * 2^-24 in [0, 1), both exact in fp32, so |z| <= sqrt(2 * 24 * ln 2) = 5.77.
+// fp32, contraction off, every operation rounded on its own. The patchify kernels and
+// erase_noise_kernel call this one function, so the tests' host replay sees the kernels' bits.
+PVR_DEV float erase_normal(uint64_t sd, uint64_t e) {
+#pragma clang fp contract(off)
+  const uint32_t h1 = rng_hash(sd, 2 * e), h2 = rng_hash(sd, 2 * e + 1);
+  const float u1 = (float)((h1 >> 8) + 1u) * 5.9604644775390625e-08f;
+  const float u2 = (float)(h2 >> 8) * 5.9604644775390625e-08f;
+  return sqrtf(-2.0f * logf(u1)) * cosf(6.2831853f * u2);
+}
+
+// The fill of pixel (s, c, y, x) of a [.][C][H][W] model image (sd: *er.seed + er.offset in ERASE_PIXEL mode)
+PVR_DEV float erase_fill(const EraseArgs& er, uint64_t sd, int s, int c, int y, int x, int C, int H, int W) {
+  if (er.mode == ERASE_PIXEL) return erase_normal(sd, (((uint64_t)s * C + c) * H + y) * W + x);
+  return pick4(er.value, c);
+}
+
+PVR_DEV bool erase_hit(const EraseRow& e, int x, int y) { return x >= e.x0 && x < e.x1 && y >= e.y0 && y < e.y1; }
+
+PVR_DEV EraseRow erase_row(const EraseRow* __restrict__ rows, int b) {
+  const int4 q = *(const int4*)(rows + b);
+  return EraseRow{q.x, q.y, q.z, q.w};
+}
+
+// The mix row of an ERASE kernel: without a plan the identity (partner = self, lam == 1, empty box), under
+// which mix_value selects the sample's own value and no partner pixel is read
+PVR_DEV MixRow erase_mix_row(const MixRow* __restrict__ mix, int b, int B) {
+  if (mix) return mix_row(mix, b, B);
+  MixRow r;
+  r.partner = b; r.lam = 1.f;
+  r.bx0 = r.by0 = r.bx1 = r.by1 = 0;
+  return r;
+}
+
+__global__ void __launch_bounds__(256) erase_noise_kernel(const uint64_t* seed_ptr, uint64_t off, float* __restrict__ out, int64_t n) {
+  const uint64_t sd = *seed_ptr + off;
+  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) out[i] = erase_normal(sd, (uint64_t)i);
+}
+
 // img [B][C][H][W] fp32 -> patches [B*np][Kp] bf16, k = (c*P + ph)*P + pw, zero padded to Kp.
 // One thread per 8 consecutive k of a patch row: with P % 8 == 0 they are 8 consecutive pixels of
 // one image row (two float4 loads, one 16-B store); the zero padding past C*P*P and other patch
@@ -242,10 +287,24 @@ PVR_DEV MixRow mix_row(const MixRow* __restrict__ mix, int b, int B) {
 // belongs to sample r / n_keep and holds patch keep[r] of it (keep [B][n_keep] int32, ascending per
 // sample: patch_keep_kernel); the pixels, the padding and the mix plan (a box is in image pixels) are
 // those of that patch in the plain kernel.
-template <bool MIX, bool KEEP = false>
+// ERASE (random erasing, both patchify kernels; only with MIX, whose plan may then be null = identity): a
+// sample's own value inside its erase box er.rows[sample] is the fill (erase_fill) instead of the pixel,
+// before the mix formula: the own and the partner pixel each test their own sample's box. An erased
+// pixel is not loaded (eight erased pixels of the vector path load nothing); the loads that remain are
+// those of the MIX kernel, inside the image. C <= 4 (the fill's per-channel value; host-checked).
+// The fills of a thread's 8 pixels stay unrolled (16 call sites per code shape, 8 - 12 k instructions per
+// instantiation): one rolled loop over the erased pixels is a third of the code but measured 10 % slower,
+// a thread's fills then running one after the other (profiles/random_erasing/).
+template <bool MIX, bool KEEP = false, bool ERASE = false>
 __global__ void __launch_bounds__(256) im2col_kernel(const float* __restrict__ img, uint16_t* __restrict__ out,
                                                       int B, int C, int H, int W, int P, int Kp,
-                                                      const MixRow* __restrict__ mix, const int* __restrict__ keep, int n_keep) {
+                                                      const MixRow* __restrict__ mix, const int* __restrict__ keep, int n_keep,
+                                                      EraseArgs er) {
+  static_assert(MIX || !ERASE, "ERASE exists only together with MIX");
+  uint64_t esd = 0;
+  if constexpr (ERASE) {
+    if (er.mode == ERASE_PIXEL) esd = *er.seed + er.offset;
+  }
   const int gw = W / P, np = (H / P) * gw;
   const int kc = C * P * P, k8 = Kp / 8;
   const bool vec = (P % 8 == 0) && (W % 4 == 0);
@@ -258,8 +317,13 @@ __global__ void __launch_bounds__(256) im2col_kernel(const float* __restrict__ i
     const int y0 = (pidx / gw) * P, x0 = (pidx % gw) * P;
     float v[8];
     if constexpr (MIX) {
-      const MixRow r = mix_row(mix, b, B);
+      const MixRow r = ERASE ? erase_mix_row(mix, b, B) : mix_row(mix, b, B);
       const float oml = 1.0f - r.lam;
+      EraseRow eo = {0, 0, 0, 0}, ep = eo;  // the own and the partner sample's erase box
+      if constexpr (ERASE) {
+        eo = erase_row(er.rows, b);
+        ep = erase_row(er.rows, r.partner);
+      }
       if (vec && k0 + 8 <= kc) {
         const int c = k0 / (P * P), rem = k0 % (P * P), ph = rem / P, pw = rem % P;
         const int y = y0 + ph, x = x0 + pw;
@@ -273,18 +337,46 @@ __global__ void __launch_bounds__(256) im2col_kernel(const float* __restrict__ i
         }
         const int64_t off = ((int64_t)c * H + y) * W + x;
         float4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, p0 = a0, p1 = a0;
-        if (n_in < 8) {
-          const float* src = img + (int64_t)b * C * H * W + off;
-          a0 = *(const float4*)src; a1 = *(const float4*)(src + 4);
-        }
-        if (n_in > 0 || r.lam != 1.f) {
-          const float* src = img + (int64_t)r.partner * C * H * W + off;
-          p0 = *(const float4*)src; p1 = *(const float4*)(src + 4);
-        }
-        const float a[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-        const float p[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
+        if constexpr (ERASE) {
+          bool ea[8], eq[8], need_a = false, need_p = false;  // the own / the partner pixel is used and erased
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = mix_value(a[j], p[j], in[j], r.lam, oml);
+          for (int j = 0; j < 8; ++j) {
+            const bool use_p = in[j] || r.lam != 1.f;
+            ea[j] = !in[j] && erase_hit(eo, x + j, y);
+            eq[j] = use_p && erase_hit(ep, x + j, y);
+            need_a |= !in[j] && !ea[j];
+            need_p |= use_p && !eq[j];
+          }
+          if (need_a) {
+            const float* src = img + (int64_t)b * C * H * W + off;
+            a0 = *(const float4*)src; a1 = *(const float4*)(src + 4);
+          }
+          if (need_p) {
+            const float* src = img + (int64_t)r.partner * C * H * W + off;
+            p0 = *(const float4*)src; p1 = *(const float4*)(src + 4);
+          }
+          const float a[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+          const float p[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const float fa = ea[j] ? erase_fill(er, esd, b, c, y, x + j, C, H, W) : a[j];
+            const float fp = eq[j] ? erase_fill(er, esd, r.partner, c, y, x + j, C, H, W) : p[j];
+            v[j] = mix_value(fa, fp, in[j], r.lam, oml);
+          }
+        } else {
+          if (n_in < 8) {
+            const float* src = img + (int64_t)b * C * H * W + off;
+            a0 = *(const float4*)src; a1 = *(const float4*)(src + 4);
+          }
+          if (n_in > 0 || r.lam != 1.f) {
+            const float* src = img + (int64_t)r.partner * C * H * W + off;
+            p0 = *(const float4*)src; p1 = *(const float4*)(src + 4);
+          }
+          const float a[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+          const float p[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
+#pragma unroll
+          for (int j = 0; j < 8; ++j) v[j] = mix_value(a[j], p[j], in[j], r.lam, oml);
+        }
       } else {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -296,8 +388,14 @@ __global__ void __launch_bounds__(256) im2col_kernel(const float* __restrict__ i
             const bool in = y >= r.by0 && y < r.by1 && x >= r.bx0 && x < r.bx1;
             const int64_t off = ((int64_t)c * H + y) * W + x;
             float a = 0.f, p = 0.f;
-            if (!in) a = img[(int64_t)b * C * H * W + off];
-            if (in || r.lam != 1.f) p = img[(int64_t)r.partner * C * H * W + off];
+            if constexpr (ERASE) {
+              if (!in) a = erase_hit(eo, x, y) ? erase_fill(er, esd, b, c, y, x, C, H, W) : img[(int64_t)b * C * H * W + off];
+              if (in || r.lam != 1.f)
+                p = erase_hit(ep, x, y) ? erase_fill(er, esd, r.partner, c, y, x, C, H, W) : img[(int64_t)r.partner * C * H * W + off];
+            } else {
+              if (!in) a = img[(int64_t)b * C * H * W + off];
+              if (in || r.lam != 1.f) p = img[(int64_t)r.partner * C * H * W + off];
+            }
             v[j] = mix_value(a, p, in, r.lam, oml);
           }
         }
@@ -345,9 +443,6 @@ PVR_DEV float u8_normalise(float p, float mean, float stdv) {
   return (p / 255.0f - mean) / stdv;
 }
 
-// a[c] of a by-value kernel argument without a divergent index into the argument segment
-PVR_DEV float pick4(const float (&a)[4], int c) { return c == 0 ? a[0] : c == 1 ? a[1] : c == 2 ? a[2] : a[3]; }
-
 // Source coordinate of output index o along one axis: box start e0, step = (e1 - e0) / n_out;
 // returns the two taps i <= j (both inside [0, n_src - 1] for any e0 / step, NaN included) and the weight of j.
 PVR_DEV void u8_axis(int o, float e0, float step, int n_src, int& i, int& j, float& w) {
@@ -380,13 +475,19 @@ PVR_DEV float u8_sample(const uint8_t* src_c, int64_t sy, int64_t sx, const floa
 // MIX (see im2col_kernel): the blend runs on the normalised fp32 values, each sample under its own
 // crop box, so the no-GEOM table then holds fp32 values instead of their bf16 roundings.
 // KEEP: as in im2col_kernel.
-template <bool GEOM, bool MIX, bool KEEP = false>
+// ERASE: as in im2col_kernel; the fill replaces the normalised value.
+template <bool GEOM, bool MIX, bool KEEP = false, bool ERASE = false>
 __global__ void __launch_bounds__(256) im2col_u8_kernel(const uint8_t* __restrict__ img, int64_t sb, int64_t sc, int64_t sy,
                                                          int64_t sx, U8Norm nrm, const float* __restrict__ geom,
                                                          uint16_t* __restrict__ out, int B, int C, int Hs, int Ws, int H, int W,
                                                          int P, int Kp, int vec, const MixRow* __restrict__ mix,
-                                                         const int* __restrict__ keep, int n_keep) {
+                                                         const int* __restrict__ keep, int n_keep, EraseArgs er) {
 #pragma clang fp contract(off)
+  static_assert(MIX || !ERASE, "ERASE exists only together with MIX");
+  uint64_t esd = 0;
+  if constexpr (ERASE) {
+    if (er.mode == ERASE_PIXEL) esd = *er.seed + er.offset;
+  }
   // Without GEOM a pixel is one of 256 byte values: each block tabulates the normalised bf16 of every
   // (channel, byte) pair once, with the same operations and hence the same bits, and its loop does
   // no division. Two correctly rounded divisions per element make the kernel ALU-bound: 51 us
@@ -412,10 +513,15 @@ __global__ void __launch_bounds__(256) im2col_u8_kernel(const uint8_t* __restric
     const uint8_t* src_b = img + b * sb;
     uint32_t h[8];  // bf16 bits
     if constexpr (MIX) {
-      const MixRow r = mix_row(mix, b, B);
+      const MixRow r = ERASE ? erase_mix_row(mix, b, B) : mix_row(mix, b, B);
       const float oml = 1.0f - r.lam;
       const uint8_t* src_p = img + r.partner * sb;
       float v[8];
+      EraseRow eo = {0, 0, 0, 0}, ep = eo;  // the own and the partner sample's erase box
+      if constexpr (ERASE) {
+        eo = erase_row(er.rows, b);
+        ep = erase_row(er.rows, r.partner);
+      }
       if constexpr (!GEOM) {
         if (vec && k0 + 8 <= kc) {
           const int c = k0 / (P * P), rem = k0 % (P * P), ph = rem / P, pw = rem % P;
@@ -430,13 +536,35 @@ __global__ void __launch_bounds__(256) im2col_u8_kernel(const uint8_t* __restric
           }
           const int64_t off = c * sc + (int64_t)y * sy + x;
           uint2 qa = {0u, 0u}, qp = {0u, 0u};
-          if (n_in < 8) qa = *(const uint2*)(src_b + off);
-          if (n_in > 0 || r.lam != 1.f) qp = *(const uint2*)(src_p + off);
+          if constexpr (ERASE) {
+            bool ea[8], eq[8], need_a = false, need_p = false;  // the own / the partner pixel is used and erased
 #pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const uint32_t a = ((j < 4 ? qa.x : qa.y) >> (8 * (j & 3))) & 0xFFu;
-            const uint32_t p = ((j < 4 ? qp.x : qp.y) >> (8 * (j & 3))) & 0xFFu;
-            v[j] = mix_value(lutf[c][a], lutf[c][p], in[j], r.lam, oml);
+            for (int j = 0; j < 8; ++j) {
+              const bool use_p = in[j] || r.lam != 1.f;
+              ea[j] = !in[j] && erase_hit(eo, x + j, y);
+              eq[j] = use_p && erase_hit(ep, x + j, y);
+              need_a |= !in[j] && !ea[j];
+              need_p |= use_p && !eq[j];
+            }
+            if (need_a) qa = *(const uint2*)(src_b + off);
+            if (need_p) qp = *(const uint2*)(src_p + off);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+              const uint32_t a = ((j < 4 ? qa.x : qa.y) >> (8 * (j & 3))) & 0xFFu;
+              const uint32_t p = ((j < 4 ? qp.x : qp.y) >> (8 * (j & 3))) & 0xFFu;
+              const float fa = ea[j] ? erase_fill(er, esd, b, c, y, x + j, C, H, W) : lutf[c][a];
+              const float fp = eq[j] ? erase_fill(er, esd, r.partner, c, y, x + j, C, H, W) : lutf[c][p];
+              v[j] = mix_value(fa, fp, in[j], r.lam, oml);
+            }
+          } else {
+            if (n_in < 8) qa = *(const uint2*)(src_b + off);
+            if (n_in > 0 || r.lam != 1.f) qp = *(const uint2*)(src_p + off);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+              const uint32_t a = ((j < 4 ? qa.x : qa.y) >> (8 * (j & 3))) & 0xFFu;
+              const uint32_t p = ((j < 4 ? qp.x : qp.y) >> (8 * (j & 3))) & 0xFFu;
+              v[j] = mix_value(lutf[c][a], lutf[c][p], in[j], r.lam, oml);
+            }
           }
         } else {
 #pragma unroll
@@ -449,8 +577,13 @@ __global__ void __launch_bounds__(256) im2col_u8_kernel(const uint8_t* __restric
               const bool in = y >= r.by0 && y < r.by1 && x >= r.bx0 && x < r.bx1;
               const int64_t off = c * sc + (int64_t)y * sy + (int64_t)x * sx;
               float a = 0.f, p = 0.f;
-              if (!in) a = lutf[c][src_b[off]];
-              if (in || r.lam != 1.f) p = lutf[c][src_p[off]];
+              if constexpr (ERASE) {
+                if (!in) a = erase_hit(eo, x, y) ? erase_fill(er, esd, b, c, y, x, C, H, W) : lutf[c][src_b[off]];
+                if (in || r.lam != 1.f) p = erase_hit(ep, x, y) ? erase_fill(er, esd, r.partner, c, y, x, C, H, W) : lutf[c][src_p[off]];
+              } else {
+                if (!in) a = lutf[c][src_b[off]];
+                if (in || r.lam != 1.f) p = lutf[c][src_p[off]];
+              }
               v[j] = mix_value(a, p, in, r.lam, oml);
             }
           }
@@ -470,8 +603,17 @@ __global__ void __launch_bounds__(256) im2col_u8_kernel(const uint8_t* __restric
             const bool in = y >= r.by0 && y < r.by1 && x >= r.bx0 && x < r.bx1;
             const float mean = pick4(nrm.mean, c), stdv = pick4(nrm.stdv, c);
             float a = 0.f, p = 0.f;
-            if (!in) a = u8_sample(src_b + c * sc, sy, sx, g, stepx, stepy, x, y, Ws, Hs, mean, stdv);
-            if (in || r.lam != 1.f) p = u8_sample(src_p + c * sc, sy, sx, gp, pstepx, pstepy, x, y, Ws, Hs, mean, stdv);
+            if constexpr (ERASE) {
+              if (!in)
+                a = erase_hit(eo, x, y) ? erase_fill(er, esd, b, c, y, x, C, H, W)
+                                        : u8_sample(src_b + c * sc, sy, sx, g, stepx, stepy, x, y, Ws, Hs, mean, stdv);
+              if (in || r.lam != 1.f)
+                p = erase_hit(ep, x, y) ? erase_fill(er, esd, r.partner, c, y, x, C, H, W)
+                                        : u8_sample(src_p + c * sc, sy, sx, gp, pstepx, pstepy, x, y, Ws, Hs, mean, stdv);
+            } else {
+              if (!in) a = u8_sample(src_b + c * sc, sy, sx, g, stepx, stepy, x, y, Ws, Hs, mean, stdv);
+              if (in || r.lam != 1.f) p = u8_sample(src_p + c * sc, sy, sx, gp, pstepx, pstepy, x, y, Ws, Hs, mean, stdv);
+            }
             v[j] = mix_value(a, p, in, r.lam, oml);
           }
         }
@@ -923,28 +1065,48 @@ extern "C" hipError_t pvr_pos_gather(const float* pos, const int* keep, float* o
   return hipGetLastError();
 }
 
+// an erase argument the kernels can take: an aligned table, a known mode, a seed in pixel mode, C <= 4
+static bool erase_args_ok(const pvr::EraseArgs& e, int C) {
+  if (!e.rows) return true;
+  if (reinterpret_cast<uintptr_t>(e.rows) % 16 || C < 1 || C > 4) return false;
+  return e.mode == pvr::ERASE_CONST || (e.mode == pvr::ERASE_PIXEL && e.seed);
+}
+
+extern "C" hipError_t pvr_erase_noise(const uint64_t* seed, uint64_t offset, float* out, int64_t n, hipStream_t s) {
+  using namespace pvr;
+  if (!seed || !out || n < 0) return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  int64_t blocks = (n + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(erase_noise_kernel, dim3((unsigned)blocks), dim3(256), 0, s, seed, offset, out, n);
+  return hipGetLastError();
+}
+
 extern "C" hipError_t pvr_im2col(const float* img, uint16_t* out, int B, int C, int H, int W, int P, int Kp,
-                                 const pvr::MixRow* mix, const int* keep, int n_keep, hipStream_t s) {
+                                 const pvr::MixRow* mix, const int* keep, int n_keep, pvr::EraseArgs erase, hipStream_t s) {
   using namespace pvr;
   if (Kp % 8 || (mix && reinterpret_cast<uintptr_t>(mix) % 16)) return hipErrorInvalidValue;
+  if (!erase_args_ok(erase, C)) return hipErrorInvalidValue;
   const int np = (H / P) * (W / P);
   if (keep && (n_keep < 1 || n_keep > np)) return hipErrorInvalidValue;
   const int64_t total = (int64_t)B * (keep ? n_keep : np) * (Kp / 8);
   if (total <= 0) return hipSuccess;
   int64_t blocks = (total + 255) / 256;
   if (blocks > 16384) blocks = 16384;
-  const auto kern = keep ? (mix ? im2col_kernel<true, true> : im2col_kernel<false, true>)
-                         : (mix ? im2col_kernel<true> : im2col_kernel<false>);
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, s, img, out, B, C, H, W, P, Kp, mix, keep, keep ? n_keep : 0);
+  const auto kern = erase.rows ? (keep ? im2col_kernel<true, true, true> : im2col_kernel<true, false, true>)
+                    : keep     ? (mix ? im2col_kernel<true, true> : im2col_kernel<false, true>)
+                               : (mix ? im2col_kernel<true> : im2col_kernel<false>);
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, s, img, out, B, C, H, W, P, Kp, mix, keep, keep ? n_keep : 0, erase);
   return hipGetLastError();
 }
 
 extern "C" hipError_t pvr_im2col_u8(const uint8_t* img, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float* mean,
                                     const float* stdv, const float* geom, uint16_t* out, int B, int C, int Hs, int Ws, int H,
                                     int W, int P, int Kp, int vec, const pvr::MixRow* mix, const int* keep, int n_keep,
-                                    hipStream_t s) {
+                                    pvr::EraseArgs erase, hipStream_t s) {
   using namespace pvr;
   if (mix && reinterpret_cast<uintptr_t>(mix) % 16) return hipErrorInvalidValue;
+  if (!erase_args_ok(erase, C)) return hipErrorInvalidValue;
   if (Kp % 8 || P <= 0 || C < 1 || C > 4 || H % P || W % P || Kp < C * P * P || Hs < 1 || Ws < 1) return hipErrorInvalidValue;
   if (!geom && (Hs != H || Ws != W)) return hipErrorInvalidValue;
   if (vec && (geom || sx != 1 || P % 8 || reinterpret_cast<uintptr_t>(img) % 8 || sb % 8 || sc % 8 || sy % 8))
@@ -959,12 +1121,15 @@ extern "C" hipError_t pvr_im2col_u8(const uint8_t* img, int64_t sb, int64_t sc, 
     nrm.mean[c] = c < C ? mean[c] : 0.f;
     nrm.stdv[c] = c < C ? stdv[c] : 1.f;
   }
-  const auto kern = keep ? (mix ? (geom ? im2col_u8_kernel<true, true, true> : im2col_u8_kernel<false, true, true>)
-                                 : (geom ? im2col_u8_kernel<true, false, true> : im2col_u8_kernel<false, false, true>))
-                         : (mix ? (geom ? im2col_u8_kernel<true, true> : im2col_u8_kernel<false, true>)
-                                : (geom ? im2col_u8_kernel<true, false> : im2col_u8_kernel<false, false>));
+  const auto kern =
+      erase.rows ? (keep ? (geom ? im2col_u8_kernel<true, true, true, true> : im2col_u8_kernel<false, true, true, true>)
+                         : (geom ? im2col_u8_kernel<true, true, false, true> : im2col_u8_kernel<false, true, false, true>))
+      : keep     ? (mix ? (geom ? im2col_u8_kernel<true, true, true> : im2col_u8_kernel<false, true, true>)
+                        : (geom ? im2col_u8_kernel<true, false, true> : im2col_u8_kernel<false, false, true>))
+                 : (mix ? (geom ? im2col_u8_kernel<true, true> : im2col_u8_kernel<false, true>)
+                        : (geom ? im2col_u8_kernel<true, false> : im2col_u8_kernel<false, false>));
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, s, img, sb, sc, sy, sx, nrm, geom, out, B, C, Hs, Ws, H, W, P, Kp,
-                     vec, mix, keep, keep ? n_keep : 0);
+                     vec, mix, keep, keep ? n_keep : 0, erase);
   return hipGetLastError();
 }
 

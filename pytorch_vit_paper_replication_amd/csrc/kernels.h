@@ -75,6 +75,26 @@ struct MixRow {
 };
 static_assert(sizeof(MixRow) == 32, "MixRow is one int32 [8] row of the plan tensor");
 
+// One sample's row of a random-erasing plan, int32 [B][4] on the device (data/random_erasing.py
+// ErasePlan), the base 16-byte aligned: the half-open box (x0, y0, x1, y1) in output (model image)
+// pixels inside which the sample's own pre(s, c, y, x) is replaced by a fill before the mix formula
+// above runs, so a partner's pixels are those of the partner's erased image. x0 == x1 or y0 == y1: the
+// sample is not erased.
+struct EraseRow {
+  int x0, y0, x1, y1;  // inside [0, W] x [0, H], x0 <= x1, y0 <= y1 (host-validated: bindings.cpp erase_args)
+};
+static_assert(sizeof(EraseRow) == 16, "EraseRow is one int32 [4] row of the erase table");
+
+// The fill: value[c] per channel (ERASE_CONST, the model's normalised space), or a standard normal
+// per element from the counter hash (ERASE_PIXEL): erase_normal(*seed + offset, e) of elementwise.hip
+// with e = ((s * C + c) * H + y) * W + x, the element's index in the model image.
+constexpr int ERASE_CONST = 0, ERASE_PIXEL = 1;
+// The patchify kernels' erase argument. rows null: no erasing (the kernels that ran before it existed).
+struct EraseArgs {
+  const EraseRow* rows = nullptr; int mode = ERASE_CONST; float value[4] = {0.f, 0.f, 0.f, 0.f};
+  const uint64_t* seed = nullptr; uint64_t offset = 0;  // ERASE_PIXEL: the step's counter and the site's offset
+};
+
 // pvr_layernorm_bwd: dx = dres + LN'(dy); dw / db / dsum (each optional) accumulate dgamma, dbeta
 // and the column sums of dx.
 struct LnBwdParams {
@@ -187,13 +207,18 @@ hipError_t pvr_pos_gather(const float* pos, const int* keep, float* out, int B, 
 // mix (both patchify kernels; null: none): the batch's MixRow plan, host-validated (bindings.cpp mix_rows).
 // keep (both; null: every patch): pvr_patch_keep's table; out then has B * n_keep rows, row r = patch
 // keep[r] of sample r / n_keep
+// erase (both; rows null: none): random erasing, the EraseRow table host-validated (bindings.cpp erase_args);
+// the erase kernels are MIX kernels, in which a null mix is the identity plan
 hipError_t pvr_im2col(const float* img, uint16_t* out, int B, int C, int H, int W, int P, int Kp, const pvr::MixRow* mix,
-                      const int* keep, int n_keep, hipStream_t s);
+                      const int* keep, int n_keep, pvr::EraseArgs erase, hipStream_t s);
 // strides in elements (= bytes); geom null: Hs == H and Ws == W. `vec`: the caller has checked the
 // 8-byte load conditions on the base pointer and strides (bindings.cpp im2col_u8).
 hipError_t pvr_im2col_u8(const uint8_t* img, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float* mean, const float* stdv,
                          const float* geom, uint16_t* out, int B, int C, int Hs, int Ws, int H, int W, int P, int Kp, int vec,
-                         const pvr::MixRow* mix, const int* keep, int n_keep, hipStream_t s);
+                         const pvr::MixRow* mix, const int* keep, int n_keep, pvr::EraseArgs erase, hipStream_t s);
+// out f32 [n] = the ERASE_PIXEL fill of elements 0 .. n - 1 at site (*seed + offset): diagnostics and the
+// tests' replay of the patchify kernels' noise (the same device function)
+hipError_t pvr_erase_noise(const uint64_t* seed, uint64_t offset, float* out, int64_t n, hipStream_t s);
 hipError_t pvr_cls_rows(const float* cls, const float* pos, uint16_t* out, int B, int D, int64_t row_stride, pvr::DropSite drop,
                         hipStream_t s);
 // inv (null: none): pvr_patch_keep's slot table of a patch-dropout step. dE is then the compact

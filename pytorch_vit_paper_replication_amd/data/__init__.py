@@ -5,9 +5,11 @@ from .device_input import DeviceInput, RandomResizedCropFlip, center_box, full_b
 from .image_folder import IMG_EXTENSIONS, ImageFolder, pil_loader
 from .loaders import NUM_WORKERS, create_dataloaders, create_synthetic_dataloaders
 from .prefetch import DevicePrefetcher, prefetch
+from .random_erasing import ErasePlan, RandomErasing, erase_reference
 from .synthetic import DeviceSyntheticLoader, SyntheticImageNet
 from . import transforms
 
 __all__ = ["ImageFolder", "pil_loader", "IMG_EXTENSIONS", "create_dataloaders", "create_synthetic_dataloaders",
            "NUM_WORKERS", "SyntheticImageNet", "DeviceSyntheticLoader", "DevicePrefetcher", "prefetch", "transforms",
-           "DeviceInput", "RandomResizedCropFlip", "full_box", "center_box", "BatchMix", "MixPlan", "mix_reference"]
+           "DeviceInput", "RandomResizedCropFlip", "full_box", "center_box", "BatchMix", "MixPlan", "mix_reference",
+           "ErasePlan", "RandomErasing", "erase_reference"]

@@ -69,13 +69,13 @@ def _fused_loss(loss_fn):
     return loss_fn
 
 
-def _mix_target(model):
-    """(whether the model's ``forward`` takes ``mix``, its image size or None): a plan is drawn for the
-    image the model sees, which for a uint8 device-input batch is not the batch's own size."""
+def _mix_target(model, keyword: str = "mix"):
+    """(whether the model's ``forward`` takes ``keyword`` (``mix`` or ``erase``), its image size or None): a plan
+    is drawn for the image the model sees, which for a uint8 device-input batch is not the batch's own size."""
     import inspect
 
     inner = getattr(model, "module", model)  # DistributedDataParallel forwards keyword arguments
-    takes = "mix" in inspect.signature(inner.forward).parameters
+    takes = keyword in inspect.signature(inner.forward).parameters
     S = getattr(inner, "config", {}).get("image_size") if takes else None
     return takes, (int(S) if S else None)
 
@@ -129,7 +129,8 @@ def _set_sampler_epoch(dataloader, epoch: Optional[int]) -> None:
 
 def train_step(model: torch.nn.Module, dataloader, loss_fn: torch.nn.Module, optimizer: torch.optim.Optimizer,
                lr_scheduler, device, *, max_grad_norm: Optional[float] = 1.0,
-               epoch: Optional[int] = None, step_logger=None, batch_mix=None, model_ema=None) -> Tuple[float, float]:
+               epoch: Optional[int] = None, step_logger=None, batch_mix=None, model_ema=None,
+               random_erasing=None) -> Tuple[float, float]:
     """One training epoch (reference GM/engine.py:9-79). Returns (train_loss, train_acc).
 
     ``batch_mix`` (optional :class:`~.data.batch_mix.BatchMix`): per batch a mixup / CutMix plan is drawn
@@ -137,6 +138,11 @@ def train_step(model: torch.nn.Module, dataloader, loss_fn: torch.nn.Module, opt
     parameter gets ``mix_reference(X, plan)`` instead), and the loss is ``soft_cross_entropy`` with the
     plan's label weights and ``batch_mix.label_smoothing`` in place of ``loss_fn``. The accuracy counts
     ``argmax == y``, the samples' own labels.
+
+    ``random_erasing`` (optional :class:`~.data.random_erasing.RandomErasing`): per batch an erase plan is
+    drawn on the host at the model's image size and passed to the model (``model(X, erase=plan)``, alone or
+    next to ``mix=``: each sample is erased, then the batch is mixed; a model whose ``forward`` has no
+    ``erase`` parameter gets ``erase_reference(X, plan)`` instead). Labels and loss are untouched.
 
     ``model_ema`` (optional :class:`~.optim.ModelEma`): attached to the optimizer on first use; a
     ``FusedAdam`` then updates the average inside its step, for any other optimizer it is updated here
@@ -150,6 +156,7 @@ def train_step(model: torch.nn.Module, dataloader, loss_fn: torch.nn.Module, opt
     model.train()
     lf = _fused_loss(loss_fn) if batch_mix is None else _SoftLoss(batch_mix.label_smoothing)
     takes_mix, mix_size = _mix_target(model) if batch_mix is not None else (False, None)
+    takes_erase, erase_size = _mix_target(model, "erase") if random_erasing is not None else (False, None)
     sums = torch.zeros(2, dtype=torch.float32, device=device)
     nb = 0
     if model_ema is not None and not model_ema.updated_by(optimizer):
@@ -159,16 +166,27 @@ def train_step(model: torch.nn.Module, dataloader, loss_fn: torch.nn.Module, opt
             step_logger.begin()
         X, y = X.to(device, non_blocking=True), y.to(device, non_blocking=True)
         with range_push("forward"):  # ROCTX ranges (PVR_ROCTX=1, rocprofv3 --marker-trace)
-            if batch_mix is None:
+            if batch_mix is None and random_erasing is None:
                 y_pred = model(X)
             else:
-                lf.plan = batch_mix.sample(X.shape[0], mix_size or X.shape[-2], mix_size or X.shape[-1])
-                if takes_mix:
-                    y_pred = model(X, mix=lf.plan)
-                else:
-                    from .data.batch_mix import mix_reference
+                Xin, kw = X, {}
+                if random_erasing is not None:  # erase each sample first, then mix the batch
+                    eplan = random_erasing.sample(X.shape[0], erase_size or X.shape[-2], erase_size or X.shape[-1])
+                    if takes_erase:
+                        kw["erase"] = eplan
+                    else:
+                        from .data.random_erasing import erase_reference
 
-                    y_pred = model(mix_reference(X, lf.plan))
+                        Xin = erase_reference(Xin, eplan)
+                if batch_mix is not None:
+                    lf.plan = batch_mix.sample(X.shape[0], mix_size or X.shape[-2], mix_size or X.shape[-1])
+                    if takes_mix:
+                        kw["mix"] = lf.plan
+                    else:
+                        from .data.batch_mix import mix_reference
+
+                        Xin = mix_reference(Xin, lf.plan)
+                y_pred = model(Xin, **kw)
             loss = lf(y_pred, y)
         optimizer.zero_grad()
         with range_push("backward"):
@@ -209,7 +227,7 @@ def train(model: torch.nn.Module, train_dataloader, test_dataloader, optimizer: 
           loss_fn: torch.nn.Module, lr_scheduler, epochs: int, device, *, max_grad_norm: Optional[float] = 1.0,
           checkpoint_dir: Optional[str] = None, metrics_path: Optional[str] = None, start_epoch: int = 0,
           results: Optional[Dict[str, List]] = None, step_metrics_path: Optional[str] = None,
-          log_every: int = 50, batch_mix=None, model_ema=None) -> Dict[str, List]:
+          log_every: int = 50, batch_mix=None, model_ema=None, random_erasing=None) -> Dict[str, List]:
     """Train and test for ``epochs`` epochs (reference GM/engine.py:132-211).
 
     ``metrics_path``: one JSONL record per epoch. ``step_metrics_path``: one JSONL record per training
@@ -217,6 +235,9 @@ def train(model: torch.nn.Module, train_dataloader, test_dataloader, optimizer: 
 
     ``batch_mix``: mixup / CutMix / label smoothing of the training batches (see :func:`train_step`);
     evaluation never mixes and keeps ``loss_fn``.
+
+    ``random_erasing``: random erasing of the training batches (see :func:`train_step`); evaluation never
+    erases.
 
     ``model_ema`` (optional :class:`~.optim.ModelEma`): averaged during training (see :func:`train_step`);
     the test pass runs inside ``model_ema.applied()``, so ``test_loss`` / ``test_acc`` are those of the
@@ -242,7 +263,7 @@ def train(model: torch.nn.Module, train_dataloader, test_dataloader, optimizer: 
         train_loss, train_acc = train_step(model=model, dataloader=train_dataloader, loss_fn=loss_fn,
                                            optimizer=optimizer, lr_scheduler=lr_scheduler, device=device,
                                            max_grad_norm=max_grad_norm, epoch=epoch, step_logger=step_logger,
-                                           batch_mix=batch_mix, model_ema=model_ema)
+                                           batch_mix=batch_mix, model_ema=model_ema, random_erasing=random_erasing)
         if step_logger is not None:
             step_logger.flush()
         with model_ema.applied() if model_ema is not None else contextlib.nullcontext():

@@ -280,14 +280,20 @@ class ViT(nn.Module):
         x = self.transformer_encoder(x)
         return self.layer_norm(x)
 
-    def forward(self, x: torch.Tensor, geom: Optional[torch.Tensor] = None, mix=None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, geom: Optional[torch.Tensor] = None, mix=None, erase=None) -> torch.Tensor:
         """``mix`` (optional :class:`~..data.batch_mix.MixPlan`, training or eval): mixup / CutMix of the
         batch as the model sees it, inside the patch-embedding kernels on the fused path and as
-        ``data.batch_mix.mix_reference`` after the preprocessing elsewhere. ``None``: no mixing."""
+        ``data.batch_mix.mix_reference`` after the preprocessing elsewhere. ``None``: no mixing.
+
+        ``erase`` (optional :class:`~..data.random_erasing.ErasePlan`, applied whenever it is passed, training
+        or eval; nothing draws one implicitly): random erasing of each sample as the model sees it, before
+        the mix, in the same kernels on the fused path (a ``"pixel"`` plan draws its noise from the step's
+        value of the dropout counter) and as ``data.random_erasing.erase_reference`` between the
+        preprocessing and the mix elsewhere. ``None``: no erasing."""
         x, pre = self._device_input(x, geom)
         if _ext.use_fused(x) and self._fused_supported(x, pre):
-            return self._forward_fused(x, pre, mix)
-        x = self._mix_reference(self._preprocess_reference(x, pre), mix)
+            return self._forward_fused(x, pre, mix, erase)
+        x = self._mix_reference(self._erase_reference(self._preprocess_reference(x, pre), erase), mix)
         x = self.forward_features(x)
         return self.classifier(x[:, 0])
 
@@ -400,6 +406,14 @@ class ViT(nn.Module):
         return preprocess_reference(x, pre[0], pre[1], pre[2], (S, S))
 
     @staticmethod
+    def _erase_reference(x: torch.Tensor, erase) -> torch.Tensor:
+        if erase is None:
+            return x
+        from ..data.random_erasing import erase_reference
+
+        return erase_reference(x, erase)  # "pixel" mode: the noise comes from torch's RNG here
+
+    @staticmethod
     def _mix_reference(x: torch.Tensor, mix) -> torch.Tensor:
         if mix is None:
             return x
@@ -442,22 +456,24 @@ class ViT(nn.Module):
         _ext.ext().rng_next(rng, seed)  # seed = rng; rng += 1 (one device kernel, graph-replay safe)
         return seed
 
-    def _forward_fused(self, x: torch.Tensor, pre=None, mix=None) -> torch.Tensor:
+    def _forward_fused(self, x: torch.Tensor, pre=None, mix=None, erase=None) -> torch.Tensor:
         from ..ops.fused_vit import HeadFn
 
         # the head reads token 0 only: the last block may return the class-token rows alone ([B, D])
-        tokens, store, B, N = self._fused_encoder(x, pre, cls_rows=True, mix=mix)
+        tokens, store, B, N = self._fused_encoder(x, pre, cls_rows=True, mix=mix, erase=erase)
         head = self.classifier[0]
         return HeadFn.apply(tokens, B, N if tokens.shape[0] == B * N else 1, self.layer_norm.eps, store, self.layer_norm.weight, self.layer_norm.bias,
                             head.weight, head.bias)
 
-    def _fused_encoder(self, x: torch.Tensor, pre=None, cls_rows: bool = False, mix=None):
+    def _fused_encoder(self, x: torch.Tensor, pre=None, cls_rows: bool = False, mix=None, erase=None):
         """Patch embedding + every encoder block on the fused path: (bf16 tokens [B*N, D], store, B, N).
         Shared by this model's head and the classifier-free backbone (models/vit_no_classifier.py).
         ``cls_rows`` (a caller that reads token 0 of each image only): the last block may run on the
         class-token rows alone (ops/fused_vit.py ``CLS_LAST_BLOCK``), and ``tokens`` is then ``[B, D]``.
         ``pre`` = ``(mean, std, geom)`` of a uint8 batch (:meth:`_device_input`), None for a float one.
-        ``mix``: the batch's ``MixPlan`` (None: none), applied by the patchify kernel."""
+        ``mix``: the batch's ``MixPlan`` (None: none), applied by the patchify kernel. ``erase``: the batch's
+        ``ErasePlan`` (None: none), likewise; a "pixel" plan takes the step's counter value even when nothing
+        else draws from it (every dropout at 0, or an evaluation forward)."""
         from ..ops.fused_vit import (ATTN_SITE, DROP_PATH_SITE, EncoderBlockClsFn, EncoderBlockFn, PatchEmbedFn, PatchEmbedU8Fn,
                                      block_links, cls_last_block_ok, site_drop)
         from ..runtime.param_store import get_store
@@ -493,16 +509,17 @@ class ViT(nn.Module):
             store.prepare_grads()
         need_seed = training and (c["mlp_dropout"] > 0 or c["embedding_dropout"] > 0 or c["attn_dropout"] > 0
                                   or any(p > 0 for p in dp_rates) or n_keep > 0)
+        need_seed = need_seed or (erase is not None and erase.mode == "pixel")
         seed = self._dropout_seed(dev) if need_seed else None
         conv = pe.patch_and_flatten[0]
         if pre is None:
             tokens = PatchEmbedFn.apply(x, c["patch_size"], store, seed, pe.dropout.p, training,
-                                        conv.weight, conv.bias, pe.class_token, pe.position_embedding, mix, n_keep)
+                                        conv.weight, conv.bias, pe.class_token, pe.position_embedding, mix, n_keep, erase)
         else:
             mean, std, geom = pre
             tokens = PatchEmbedU8Fn.apply(x, geom, mean, std, (c["image_size"], c["image_size"]), c["patch_size"], store, seed,
                                           pe.dropout.p, training, conv.weight, conv.bias, pe.class_token,
-                                          pe.position_embedding, mix, n_keep)
+                                          pe.position_embedding, mix, n_keep, erase)
         B = x.shape[0]
         N = (n_keep or pe.number_of_patches) + 1  # the encoder's tokens per sample
         f8 = self._fp8_state(dev, B * N)

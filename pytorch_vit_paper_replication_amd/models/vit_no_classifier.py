@@ -28,15 +28,16 @@ class ViT(_FullViT):
         del self.classifier
         self.config.pop("num_classes", None)
 
-    def forward(self, x: torch.Tensor, geom: Optional[torch.Tensor] = None, mix=None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, geom: Optional[torch.Tensor] = None, mix=None, erase=None) -> torch.Tensor:
         x, pre = self._device_input(x, geom)  # uint8 batches after set_device_input (models/vit.py)
         if _ext.use_fused(x) and self._fused_supported(x, pre):
-            return self._forward_fused_features(x, pre, mix)
-        return self.forward_features(self._mix_reference(self._preprocess_reference(x, pre), mix))  # mix: a MixPlan, as models/vit.py
+            return self._forward_fused_features(x, pre, mix, erase)
+        # mix: a MixPlan, erase: an ErasePlan, as models/vit.py
+        return self.forward_features(self._mix_reference(self._erase_reference(self._preprocess_reference(x, pre), erase), mix))
 
-    def _forward_fused_features(self, x: torch.Tensor, pre=None, mix=None) -> torch.Tensor:
+    def _forward_fused_features(self, x: torch.Tensor, pre=None, mix=None, erase=None) -> torch.Tensor:
         from ..ops.fused_vit import TokenLayerNormFn
 
-        tokens, store, B, N = self._fused_encoder(x, pre, mix=mix)  # the full ViT's fused encoder (device checks, side-stream join)
+        tokens, store, B, N = self._fused_encoder(x, pre, mix=mix, erase=erase)  # the full ViT's fused encoder (device checks, side-stream join)
         y = TokenLayerNormFn.apply(tokens, self.layer_norm.eps, store, self.layer_norm.weight, self.layer_norm.bias)
         return y.float().view(B, N, -1)

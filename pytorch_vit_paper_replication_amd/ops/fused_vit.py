@@ -31,6 +31,9 @@ DROP_PATH_SITE = 1 << 21
 # patch dropout: the keys that rank a sample's patches (csrc/elementwise.hip patch_keep_kernel) are the
 # hashes of site PATCH_DROP_SITE (disjoint from 0 .. 2 L, ATTN_SITE + i and DROP_PATH_SITE + k)
 PATCH_DROP_SITE = 1 << 22
+# random erasing: the "pixel" fill's normals (csrc/elementwise.hip erase_normal) are drawn from the hashes of
+# site ERASE_SITE (disjoint from 0 .. 2 L, ATTN_SITE + i, DROP_PATH_SITE + k and PATCH_DROP_SITE)
+ERASE_SITE = 1 << 23
 
 
 # Test hook: called as DGRAD_TAP(which, output) after every encoder-block dgrad GEMM (which = 0 fc2,
@@ -144,23 +147,48 @@ def _mix_args(mix, B, size, device):
     return dict(mix=mix.on(device)[0], mix_host=mix.rows)
 
 
+def _erase_args(erase, B, C, size, device, seed):
+    """The patchify kernels' erase arguments for a ``data.random_erasing.ErasePlan`` (None: none, today's
+    call): the device table, the host copy the binding validates, mode and value, and for the "pixel"
+    mode the step's counter ``seed`` with the offset of ``ERASE_SITE``."""
+    if erase is None:
+        return {}
+    erase.check(B, size)
+    kw = dict(erase=erase.on(device), erase_host=erase.rows, erase_mode=erase.mode)
+    if erase.mode == "pixel":
+        if seed is None:
+            raise ValueError("a \"pixel\" ErasePlan needs the step's dropout counter (seed)")
+        kw.update(erase_seed=seed, erase_offset=ERASE_SITE << SITE_SHIFT)
+    else:
+        kw.update(erase_value=list(erase.channel_values(C)))
+    return kw
+
+
+def erase_noise(seed, B: int, C: int, H: int, W: int):
+    """The "pixel" fill of a ``[B, C, H, W]`` batch at the counter value ``seed``: what the patchify kernels
+    write inside the erase boxes of that step (``ext.erase_noise`` at ``ERASE_SITE``)."""
+    return _ext.ext().erase_noise(seed, ERASE_SITE << SITE_SHIFT, B, C, H, W)
+
+
 class PatchEmbedFn(torch.autograd.Function):
-    """``mix`` (optional ``MixPlan``): mixup / CutMix inside the gather, here and in PatchEmbedU8Fn."""
+    """``mix`` (optional ``MixPlan``): mixup / CutMix inside the gather, here and in PatchEmbedU8Fn.
+    ``erase`` (optional ``ErasePlan``): random erasing of each sample before the mix, likewise."""
 
     @staticmethod
-    def forward(ctx, img, patch, store, seed, p_drop, training, conv_w, conv_b, cls, pos, mix=None, n_keep=0):
+    def forward(ctx, img, patch, store, seed, p_drop, training, conv_w, conv_b, cls, pos, mix=None, n_keep=0, erase=None):
         img = img.float().contiguous()
         B, C, H, W = img.shape
         n_p, kc, kp = _patch_geometry(C, H, W, patch)
         table = patch_keep(seed, B, n_p, n_keep)
         patches = torch.empty(B * (n_keep or n_p), kp, dtype=torch.bfloat16, device=img.device)
-        _ext.ext().im2col(img, patches, patch, kp, **_mix_args(mix, B, (H, W), img.device), **_keep_arg(table))
+        _ext.ext().im2col(img, patches, patch, kp, **_mix_args(mix, B, (H, W), img.device), **_keep_arg(table),
+                          **_erase_args(erase, B, C, (H, W), img.device, seed))
         return _patch_embed_fwd(ctx, patches, B, n_p, kc, kp, store, seed, p_drop, training, conv_w, conv_b, cls, pos, table)
 
     @staticmethod
     def backward(ctx, dtokens):
         _patch_embed_bwd(ctx, dtokens)
-        return (None,) * 12
+        return (None,) * 13
 
 
 class PatchEmbedU8Fn(torch.autograd.Function):
@@ -170,20 +198,21 @@ class PatchEmbedU8Fn(torch.autograd.Function):
     while it writes the patch rows (data/device_input.py). ``geom`` None needs Hs x Ws == H x W."""
 
     @staticmethod
-    def forward(ctx, img, geom, mean, std, size, patch, store, seed, p_drop, training, conv_w, conv_b, cls, pos, mix=None, n_keep=0):
+    def forward(ctx, img, geom, mean, std, size, patch, store, seed, p_drop, training, conv_w, conv_b, cls, pos, mix=None, n_keep=0,
+                erase=None):
         B, C = img.shape[0], img.shape[1]
         H, W = size
         n_p, kc, kp = _patch_geometry(C, H, W, patch)
         table = patch_keep(seed, B, n_p, n_keep)
         patches = torch.empty(B * (n_keep or n_p), kp, dtype=torch.bfloat16, device=img.device)
         _ext.ext().im2col_u8(img, patches, list(mean), list(std), geom, H, W, patch, kp, **_mix_args(mix, B, (H, W), img.device),
-                             **_keep_arg(table))
+                             **_keep_arg(table), **_erase_args(erase, B, C, (H, W), img.device, seed))
         return _patch_embed_fwd(ctx, patches, B, n_p, kc, kp, store, seed, p_drop, training, conv_w, conv_b, cls, pos, table)
 
     @staticmethod
     def backward(ctx, dtokens):
         _patch_embed_bwd(ctx, dtokens)
-        return (None,) * 16
+        return (None,) * 17
 
 
 # test hook: bf16 outputs left unwritten on the fp8 path (only their fp8 copies are consumed) are
