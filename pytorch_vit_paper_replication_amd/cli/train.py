@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import argparse
 import contextlib
+import math
 
 import torch
 
@@ -73,6 +74,12 @@ def build_parser():
                    help="with --device-preprocess: random-resized-crop + horizontal flip on the device in training")
     p.add_argument("--source-size", type=int, default=None,
                    help="with --device-preprocess: side of the uint8 images the loader yields (default: --image-size)")
+    p.add_argument("--three-augment", action="store_true",
+                   help="with --device-preprocess: DeiT-III's 3-Augment on the device in training, one of grayscale, "
+                        "solarize or Gaussian blur per image")
+    p.add_argument("--color-jitter", type=float, default=0.0, metavar="V",
+                   help="with --device-preprocess: brightness / contrast / saturation jitter on the device in training, "
+                        "factors uniform in [max(0, 1 - V), 1 + V] (0: off; the recipes use 0.3 or 0.4)")
     p.add_argument("--mixup", type=float, default=0.0, metavar="A", help="mixup with lam ~ Beta(A, A) (0: off)")
     p.add_argument("--cutmix", type=float, default=0.0, metavar="A", help="CutMix with lam ~ Beta(A, A) (0: off)")
     p.add_argument("--mix-prob", type=float, default=1.0, help="probability that a batch is mixed")
@@ -114,6 +121,18 @@ def build_random_erasing(args, rank: int = 0):
     return RandomErasing(prob=args.random_erasing, mode=args.random_erasing_mode, generator=gen)
 
 
+def build_color_augment(args, rank: int = 0):
+    """The :class:`~..data.color_augment.ColorAugment` of ``--three-augment`` / ``--color-jitter`` (None when both are
+    off), its generator seeded from ``--seed`` per rank."""
+    if not args.three_augment and args.color_jitter <= 0:
+        return None
+    from ..data.color_augment import ColorAugment
+
+    gen = torch.Generator().manual_seed(args.seed * 1_000_003 + 32452843 + rank)
+    return ColorAugment(three_augment=args.three_augment, jitter=(args.color_jitter,) * 3 if args.color_jitter > 0 else None,
+                        generator=gen)
+
+
 def main(argv=None) -> int:
     from .. import engine
     from ..data import DeviceInput, RandomResizedCropFlip, create_dataloaders, create_synthetic_dataloaders
@@ -148,6 +167,10 @@ def main(argv=None) -> int:
         raise SystemExit("--model-ema-warmup needs --model-ema")
     if not args.device_preprocess and (args.augment != "none" or args.source_size is not None):
         raise SystemExit("--augment and --source-size need --device-preprocess")
+    if not args.device_preprocess and (args.three_augment or args.color_jitter != 0):
+        raise SystemExit("--three-augment and --color-jitter need --device-preprocess")
+    if not (args.color_jitter >= 0.0 and math.isfinite(args.color_jitter)):
+        raise SystemExit("--color-jitter must be a finite value >= 0")
     src_size = args.source_size or args.image_size
     rank, world, device = init_distributed()
     set_seeds(args.seed)
@@ -173,7 +196,7 @@ def main(argv=None) -> int:
             # per-rank crop draws: every rank augments its own shard differently (not saved by --resume)
             gen = torch.Generator().manual_seed(args.seed * 1_000_003 + rank)
             aug = RandomResizedCropFlip(generator=gen) if args.augment == "rrc-flip" else None
-            model.set_device_input(DeviceInput(augment=aug))
+            model.set_device_input(DeviceInput(augment=aug, color=build_color_augment(args, rank)))
     model.to(device)
     groups = param_groups_weight_decay(model, args.weight_decay)
     if args.optimizer == "lamb":

@@ -689,6 +689,74 @@ int64_t im2col_u8(torch::Tensor img, torch::Tensor out, std::vector<double> mean
   return vec;
 }
 
+// Colour augmentation of a raw uint8 [B, 3, Hs, Ws] batch (csrc/color.hip; data/color_augment.py ColorPlan):
+// returns a new batch (the layout of `img` when that is dense, contiguous otherwise); `img` is untouched.
+// `plan`: float32 [B, 20] ColorRow table on the image's device; `host`: the CPU tensor it was uploaded from
+// (without it the device table is read back, which synchronises). Everything is validated on the host copy
+// before any launch.
+torch::Tensor color_u8(torch::Tensor img, torch::Tensor plan, c10::optional<torch::Tensor> host) {
+  TORCH_CHECK(img.is_cuda() && img.scalar_type() == torch::kUInt8, "color_u8: img must be a uint8 GPU tensor, got ", img.scalar_type(),
+              " on ", img.device());
+  TORCH_CHECK(img.dim() == 4, "color_u8: img must be [B, 3, Hs, Ws], got ", img.dim(), " dims");
+  const int64_t B = img.size(0), C = img.size(1), Hs = img.size(2), Ws = img.size(3);
+  TORCH_CHECK(C == 3, "color_u8: colour augmentation takes 3 channels, got ", C);
+  TORCH_CHECK(Hs >= 1 && Ws >= 1 && Hs * Ws <= (int64_t(1) << 24), "color_u8: bad source size ", Hs, "x", Ws,
+              " (at most 2^24 pixels: the luma sum is 32 bits wide)");
+  TORCH_CHECK(B < (1ll << 31), "color_u8: sizes exceed 32 bits");
+  constexpr int64_t RW = sizeof(pvr::ColorRow) / 4;
+  TORCH_CHECK(plan.is_cuda() && plan.device() == img.device(), "color_u8: plan must be on the image's device");
+  TORCH_CHECK(plan.scalar_type() == torch::kFloat32 && plan.dim() == 2 && plan.size(0) == B && plan.size(1) == RW && plan.is_contiguous(),
+              "color_u8: plan must be contiguous float32 [", B, ", ", RW, "], got [", plan.size(0), ", ", plan.dim() == 2 ? plan.size(1) : -1,
+              "]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(plan.data_ptr()) % 16 == 0, "color_u8: plan must be 16-byte aligned");
+  torch::Tensor h;
+  if (host.has_value() && host->defined()) {
+    TORCH_CHECK(!host->is_cuda() && host->scalar_type() == torch::kFloat32 && host->dim() == 2 && host->size(0) == B &&
+                    host->size(1) == RW && host->is_contiguous(),
+                "color_u8: plan_host must be a contiguous CPU float32 [", B, ", ", RW, "] tensor");
+    h = *host;
+  } else {
+    h = plan.cpu();
+  }
+  const auto* rows = reinterpret_cast<const pvr::ColorRow*>(h.data_ptr());
+  bool any_blur = false, any_sum = false;
+  for (int64_t b = 0; b < B; ++b) {
+    const pvr::ColorRow& r = rows[b];
+    TORCH_CHECK(r.op >= pvr::COLOR_NONE && r.op <= pvr::COLOR_BLUR, "color_u8: row ", b, " has op ", r.op, " outside 0..3");
+    TORCH_CHECK(r.order >= 0 && r.order < 6, "color_u8: row ", b, " has order ", r.order, " outside 0..5");
+    for (float f : {r.fb, r.fc, r.fs})
+      TORCH_CHECK(std::isfinite(f) && f >= 0.f, "color_u8: row ", b, " has a jitter factor ", f, " that is not finite and >= 0");
+    if (r.op == pvr::COLOR_BLUR) {
+      TORCH_CHECK(r.sigma > 0.f && r.sigma <= pvr::COLOR_SIGMA_MAX, "color_u8: row ", b, " has sigma ", r.sigma, " outside (0, ",
+                  pvr::COLOR_SIGMA_MAX, "]");
+      double sum = 0.0;
+      for (float w : r.w) {
+        TORCH_CHECK(std::isfinite(w) && w >= 0.f && w <= 1.f, "color_u8: row ", b, " has a blur weight ", w, " outside [0, 1]");
+        sum += w;
+      }
+      TORCH_CHECK(std::fabs(sum - 1.0) < 1e-5, "color_u8: row ", b, "'s blur weights sum to ", sum, ", not 1");
+      any_blur = true;
+    }
+    any_sum = any_sum || r.fc != 1.f;
+  }
+  auto out = torch::empty_like(img);  // dense inputs keep their strides
+  if (B == 0) return out;
+  const int64_t isb = img.stride(0), isc = img.stride(1), isy = img.stride(2), isx = img.stride(3);
+  const int64_t osb = out.stride(0), osc = out.stride(1), osy = out.stride(2), osx = out.stride(3);
+  TORCH_CHECK(isb >= 0 && isc >= 0 && isy >= 0 && isx >= 0, "color_u8: negative strides");
+  const uint8_t* ip = img.data_ptr<uint8_t>();
+  uint8_t* op = out.data_ptr<uint8_t>();
+  const auto al8 = [](const uint8_t* p, int64_t sb, int64_t sc, int64_t sy, int64_t sx) {
+    return sx == 1 && reinterpret_cast<uintptr_t>(p) % 8 == 0 && sb % 8 == 0 && sc % 8 == 0 && sy % 8 == 0;
+  };
+  const int vec = Ws % 8 == 0 && al8(ip, isb, isc, isy, isx) && al8(op, osb, osc, osy, osx);
+  auto sums = torch::empty({B}, plan.options().dtype(torch::kInt32));
+  check(pvr_color_u8(ip, isb, isc, isy, isx, op, osb, osc, osy, osx, reinterpret_cast<const pvr::ColorRow*>(plan.data_ptr()),
+                     reinterpret_cast<uint32_t*>(sums.data_ptr()), (int)B, (int)Hs, (int)Ws, vec, (int)any_blur, (int)any_sum, stream()),
+        "color_u8");
+  return out;
+}
+
 // xent for soft target rows (mixed label pairs ya / yb with per-row weight lam, label smoothing eps;
 // csrc/xent.hip xent_soft_kernel): same outputs as xent, `correct` against ya
 torch::Tensor xent_soft(torch::Tensor logits, torch::Tensor ya, torch::Tensor yb, torch::Tensor lam, double eps,
@@ -1556,6 +1624,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("keep") = py::none(), py::arg("erase") = py::none(), py::arg("erase_host") = py::none(),
         py::arg("erase_mode") = "const", py::arg("erase_value") = std::vector<double>{0.0}, py::arg("erase_seed") = py::none(),
         py::arg("erase_offset") = 0);
+  m.def("color_u8", &color_u8, py::arg("img"), py::arg("plan"), py::arg("plan_host") = py::none());
   m.def("erase_noise", &erase_noise, py::arg("seed"), py::arg("site_offset"), py::arg("B"), py::arg("C"), py::arg("H"), py::arg("W"));
   m.def("patch_keep_table", &patch_keep_table, py::arg("seed"), py::arg("site_offset"), py::arg("B"), py::arg("n_p"), py::arg("n_keep"));
   m.def("pos_gather", &pos_gather, py::arg("pos"), py::arg("keep"));

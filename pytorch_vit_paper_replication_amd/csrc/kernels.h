@@ -95,6 +95,23 @@ struct EraseArgs {
   const uint64_t* seed = nullptr; uint64_t offset = 0;  // ERASE_PIXEL: the step's counter and the site's offset
 };
 
+// One sample's row of a colour-augmentation plan, 20 words [B][20] on the device (data/color_augment.py
+// ColorPlan, a float32 tensor whose first two words hold int32 bits), the base 16-byte aligned: the op, then
+// the jitter steps brightness / contrast / saturation with factors fb / fc / fs in the order `order`
+// (index into bcs, bsc, cbs, csb, sbc, scb). w: the blur's 13 normalised taps (COLOR_BLUR rows).
+// Host-validated (bindings.cpp color_u8).
+constexpr int COLOR_NONE = 0, COLOR_GRAY = 1, COLOR_SOLARIZE = 2, COLOR_BLUR = 3;
+constexpr int COLOR_TAPS = 13;        // taps -6 .. 6: sigma <= COLOR_SIGMA_MAX keeps ceil(3 sigma) inside
+constexpr float COLOR_SIGMA_MAX = 2.0f;
+constexpr int COLOR_BLOCK_PX = 2048;  // pixels of one sample per workgroup of the sum and apply kernels
+struct ColorRow {
+  int op, order;
+  float fb, fc, fs, sigma;
+  float w[COLOR_TAPS];
+  float pad;
+};
+static_assert(sizeof(ColorRow) == 80, "ColorRow is one 20-word row of the plan tensor");
+
 // pvr_layernorm_bwd: dx = dres + LN'(dy); dw / db / dsum (each optional) accumulate dgamma, dbeta
 // and the column sums of dx.
 struct LnBwdParams {
@@ -219,6 +236,13 @@ hipError_t pvr_im2col_u8(const uint8_t* img, int64_t sb, int64_t sc, int64_t sy,
 // out f32 [n] = the ERASE_PIXEL fill of elements 0 .. n - 1 at site (*seed + offset): diagnostics and the
 // tests' replay of the patchify kernels' noise (the same device function)
 hipError_t pvr_erase_noise(const uint64_t* seed, uint64_t offset, float* out, int64_t n, hipStream_t s);
+// Colour augmentation of a uint8 [B, 3, Hs, Ws] batch (csrc/color.hip): out = the op and the jitter of every
+// sample's row, `in` untouched. Both batches through element strides; `vec`: the caller has checked the 8-byte
+// access conditions on both (bindings.cpp color_u8). sums: uint32 [B] scratch, cleared on the stream here.
+// any_blur / any_sum: some row has op COLOR_BLUR / a contrast factor other than 1 (else that kernel is not launched).
+hipError_t pvr_color_u8(const uint8_t* in, int64_t isb, int64_t isc, int64_t isy, int64_t isx, uint8_t* out, int64_t osb, int64_t osc,
+                        int64_t osy, int64_t osx, const pvr::ColorRow* rows, uint32_t* sums, int B, int Hs, int Ws, int vec,
+                        int any_blur, int any_sum, hipStream_t s);
 hipError_t pvr_cls_rows(const float* cls, const float* pos, uint16_t* out, int B, int D, int64_t row_stride, pvr::DropSite drop,
                         hipStream_t s);
 // inv (null: none): pvr_patch_keep's slot table of a patch-dropout step. dE is then the compact

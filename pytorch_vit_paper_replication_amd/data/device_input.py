@@ -96,12 +96,15 @@ class DeviceInput:
 
     ``mean`` / ``std``: per-channel normalisation of the [0, 1]-scaled image; ``None`` means 0 / 1,
     the reference's ``default_vit_transform`` (scale only). ``augment``: a sampler of per-sample crop
-    boxes (:class:`RandomResizedCropFlip`) the model draws from in training mode.
+    boxes (:class:`RandomResizedCropFlip`) the model draws from in training mode. ``color``: a sampler of
+    per-sample colour plans (:class:`~.color_augment.ColorAugment`) the model draws from in training mode
+    likewise; the colour stage runs on the source batch, before the crop.
     """
 
     mean: Optional[Sequence[float]] = None
     std: Optional[Sequence[float]] = None
     augment: Optional[RandomResizedCropFlip] = None
+    color: Optional["ColorAugment"] = None  # noqa: F821 (data/color_augment.py)
 
     def mean_std(self, channels: int = 3) -> Tuple[Tuple[float, ...], Tuple[float, ...]]:
         mean = (0.0,) * channels if self.mean is None else tuple(float(m) for m in self.mean)

@@ -280,7 +280,7 @@ class ViT(nn.Module):
         x = self.transformer_encoder(x)
         return self.layer_norm(x)
 
-    def forward(self, x: torch.Tensor, geom: Optional[torch.Tensor] = None, mix=None, erase=None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, geom: Optional[torch.Tensor] = None, mix=None, erase=None, color=None) -> torch.Tensor:
         """``mix`` (optional :class:`~..data.batch_mix.MixPlan`, training or eval): mixup / CutMix of the
         batch as the model sees it, inside the patch-embedding kernels on the fused path and as
         ``data.batch_mix.mix_reference`` after the preprocessing elsewhere. ``None``: no mixing.
@@ -289,7 +289,14 @@ class ViT(nn.Module):
         or eval; nothing draws one implicitly): random erasing of each sample as the model sees it, before
         the mix, in the same kernels on the fused path (a ``"pixel"`` plan draws its noise from the step's
         value of the dropout counter) and as ``data.random_erasing.erase_reference`` between the
-        preprocessing and the mix elsewhere. ``None``: no erasing."""
+        preprocessing and the mix elsewhere. ``None``: no erasing.
+
+        ``color`` (optional :class:`~..data.color_augment.ColorPlan`, applied whenever it is passed; in training
+        mode the model draws one from ``DeviceInput.color`` when that is set): colour augmentation of the raw
+        uint8 source batch, before everything else (the crop included), by the kernels of ``csrc/color.hip`` on
+        the fused path and as ``data.color_augment.color_reference`` elsewhere. It needs a uint8 batch and
+        :meth:`set_device_input`. ``None``: none."""
+        x = self._color_stage(x, color)
         x, pre = self._device_input(x, geom)
         if _ext.use_fused(x) and self._fused_supported(x, pre):
             return self._forward_fused(x, pre, mix, erase)
@@ -396,6 +403,29 @@ class ViT(nn.Module):
                 raise ValueError(f"geom must be [{B}, 4] (x0, y0, x1, y1) rows, got {tuple(geom.shape)}")
             geom = geom.to(device=x.device, dtype=torch.float32, non_blocking=True).contiguous()
         return x, (mean, std, geom)
+
+    def _color_stage(self, x: torch.Tensor, color) -> torch.Tensor:
+        """The colour stage of ``forward(color=...)`` on the raw batch: ``x`` itself without a plan (an explicit
+        one, or in training mode a draw from ``DeviceInput.color``), else a new uint8 batch of the same layout."""
+        spec = getattr(self, "_device_input_spec", None)
+        u8 = spec is not None and x.dtype == torch.uint8
+        if color is None:
+            sampler = getattr(spec, "color", None) if u8 and self.training else None
+            if sampler is None:
+                return x
+            color = sampler.sample(x.shape[0])  # raises under a stream capture: a replay would reuse one draw
+        elif not u8:
+            raise ValueError("forward(color=...) needs a uint8 batch and set_device_input(spec)")
+        if x.dim() != 4:
+            raise ValueError(f"uint8 input must be [B, C, Hs, Ws], got {tuple(x.shape)}")
+        color.check(x.shape[0])
+        if _ext.use_fused(x):  # the stage does not depend on the model's shape
+            from ..ops.fused_vit import color_u8
+
+            return color_u8(x, color)
+        from ..data.color_augment import color_reference
+
+        return color_reference(x, color)
 
     def _preprocess_reference(self, x: torch.Tensor, pre) -> torch.Tensor:
         if pre is None:

@@ -28,7 +28,8 @@ class ViT(_FullViT):
         del self.classifier
         self.config.pop("num_classes", None)
 
-    def forward(self, x: torch.Tensor, geom: Optional[torch.Tensor] = None, mix=None, erase=None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, geom: Optional[torch.Tensor] = None, mix=None, erase=None, color=None) -> torch.Tensor:
+        x = self._color_stage(x, color)  # color: a ColorPlan on the raw uint8 batch, as models/vit.py
         x, pre = self._device_input(x, geom)  # uint8 batches after set_device_input (models/vit.py)
         if _ext.use_fused(x) and self._fused_supported(x, pre):
             return self._forward_fused_features(x, pre, mix, erase)

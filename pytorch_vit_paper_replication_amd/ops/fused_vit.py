@@ -170,6 +170,16 @@ def erase_noise(seed, B: int, C: int, H: int, W: int):
     return _ext.ext().erase_noise(seed, ERASE_SITE << SITE_SHIFT, B, C, H, W)
 
 
+def color_u8(x, plan):
+    """The colour stage of a ``data.color_augment.ColorPlan`` on a raw uint8 ``[B, 3, Hs, Ws]`` GPU batch (contiguous or
+    ``channels_last``): a new uint8 batch of the same shape and layout from the kernels of ``csrc/color.hip``; ``x``
+    is untouched. No autograd: images carry no gradient."""
+    if x.dim() != 4:
+        raise ValueError(f"color_u8: expected [B, 3, Hs, Ws], got {tuple(x.shape)}")
+    plan.check(x.shape[0])
+    return _ext.ext().color_u8(x, plan.on(x.device), plan.rows)
+
+
 class PatchEmbedFn(torch.autograd.Function):
     """``mix`` (optional ``MixPlan``): mixup / CutMix inside the gather, here and in PatchEmbedU8Fn.
     ``erase`` (optional ``ErasePlan``): random erasing of each sample before the mix, likewise."""
