@@ -35,6 +35,13 @@ def check_source_hash(so, csrc) -> str:
     return want
 
 
+def _apply_env_switches(mod) -> None:
+    """Environment switches read once, when the extension is imported. ``PVR_GEMM_LEAN=0``: every GEMM
+    launch takes the general kernel instead of a lean instantiation (``ext().set_gemm_lean(False)``)."""
+    if os.environ.get("PVR_GEMM_LEAN", "1") == "0":
+        mod.set_gemm_lean(False)
+
+
 def load():
     """Import the compiled extension once; returns the module or None.
 
@@ -65,6 +72,7 @@ def load():
             from . import _C as mod  # noqa: F401  (built in-tree)
 
         _C = mod
+        _apply_env_switches(mod)
     except BaseException as e:  # pragma: no cover - depends on build state
         _ERR = e
         if os.environ.get("PVR_AUTOBUILD", "0") == "1":
@@ -79,6 +87,7 @@ def load():
 
                 _C = mod2
                 _ERR = None
+                _apply_env_switches(mod2)
             except BaseException as e2:
                 _ERR = e2
     return _C

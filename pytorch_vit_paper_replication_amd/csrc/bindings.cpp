@@ -149,6 +149,8 @@ void attach_tail(pvr::GemmParams& p, const torch::Tensor& like) {
   p.tail_cnt_elems = (int)it->second.cnt.numel();
 }
 void set_gemm_tail(bool on) { g_gemm_tail = on; }
+// Lean GEMM instantiations (csrc/gemm_lean.h) on / off (_ext.py turns them off for PVR_GEMM_LEAN=0)
+void set_gemm_lean(bool on) { pvr_set_gemm_lean(on ? 1 : 0); }
 
 // Counters of the in-launch split-K reduction (GemmParams::sk_*): per (device, stream) two words
 // per output tile plus a timeout count, zeroed once; every launch leaves the tile words zero.
@@ -1583,6 +1585,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("set_deterministic", &set_deterministic, "deterministic reductions (partial rows + ordered sum) instead of float atomics");
   m.def("deterministic", &deterministic);
   m.def("set_gemm_tail", &set_gemm_tail, "split-K tail of the last dispatch round on (True, default) / off (A/B)");
+  m.def("set_gemm_lean", &set_gemm_lean,
+        "lean GEMM instantiations on (True, default; PVR_GEMM_LEAN=0 at import: off) / off: every launch takes the general kernel");
+  m.def("gemm_lean_last", [] { return (int64_t)pvr_gemm_lean_last(); },
+        "GemmLean bits (csrc/gemm_lean.h) of the kernel the most recent gemm launched; 0: a general kernel");
   m.def("gemm", &gemm,py::arg("A"), py::arg("a_kcontig"), py::arg("B"), py::arg("b_kcontig"), py::arg("C"),
         py::arg("M"), py::arg("N"), py::arg("K"), py::arg("epi"), py::arg("bias"), py::arg("resid"), py::arg("addend"),
         py::arg("addend_period"), py::arg("aux"), py::arg("row_group"), py::arg("row_stride_group"),

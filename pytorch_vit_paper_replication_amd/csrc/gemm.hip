@@ -19,6 +19,7 @@
 // flight while the MFMAs of tile t run.
 #include "common.h"
 #include "kernels.h"
+#include "gemm_lean.h"
 #include <type_traits>
 
 namespace pvr {
@@ -1025,34 +1026,41 @@ PVR_DEV void pp_phase(v4f (&acc)[8][4], v8s (&af)[4][2], v8s (&bf)[2][2][2], v8s
 // LDS). Buffer resources start at the wave's first row: rows past M read 0 and are not written;
 // lanes whose columns are past N use an out-of-range offset. Same fp32 math as `epilogue` above.
 // epilogue_direct's preconditions: plain row mapping, 16-B column groups, 31-bit buffer offsets
-__host__ __device__ inline bool direct_ok(const GemmParams& p) {
-  const int64_t l1 = p.ldc > p.ld_resid ? p.ldc : p.ld_resid;
-  const int64_t ld = l1 > p.ld_aux ? l1 : p.ld_aux;
-  return !p.addend && !p.row_group && (p.N & 7) == 0 && (int64_t)p.M * ld * 2 < (1ll << 31);
-}
+__host__ __device__ inline bool direct_ok(const GemmParams& p) { return direct_ok_c(p); }
 
-template <int EPI, bool RES, bool SCALED = false>
+//
+// LN != 0 (GemmLean bits, bf16 operands only): a lean instantiation. Bias, dropout, aux and column
+// sums are what the bits say instead of run-time tests of p (the host's lean_choose guarantees that
+// they match, that the dropout indices fit 32 bits and that c_skip / dbg are off). The arithmetic is
+// the general form's with that option set, operation for operation; without a bias the add of the
+// 0.0f the general form loads stays (x + 0.0f turns a -0 into +0).
+template <int EPI, bool RES, bool SCALED = false, int LN = 0>
 PVR_DEV void epilogue_direct(const GemmParams& p, v4f (&acc)[8][4], char* smem, int mb, int nb, int wm, int wn, int lane) {
   typedef uint32_t v4u __attribute__((ext_vector_type(4)));
   typedef uint32_t v2u_q __attribute__((ext_vector_type(2)));
+  constexpr bool LEAN = LN != 0;
+  static_assert(!LEAN || !SCALED, "lean instantiations: bf16 operands");
+  // (the options are tested where the general form tests p, each as LEAN ? bit : p's field, so the
+  // general form's instruction stream stays what it was)
+  constexpr bool L_BIAS = (LN & LEAN_BIAS) != 0, L_DROP = (LN & LEAN_DROP) != 0;
   const int li = lane & 15, g = lane >> 4;
   const float deq = SCALED ? (*p.scale_a) * (*p.scale_b) : 1.f;  // fp8 operands: per-tensor dequant
   // rows [mb, min(M, mb + 128)) of C (and of the residual / aux tensors) from the wave's first row
   const int rows = max(0, min(128, p.M - mb));
   const uint32_t OOB = 0x80000000u;
   const __amdgpu_buffer_rsrc_t crs =
-      make_rsrc((const uint16_t*)p.C + (int64_t)mb * p.ldc, rows && !p.c_skip ? (uint32_t)(((int64_t)(rows - 1) * p.ldc + p.N) * 2) : 0);
+      make_rsrc((const uint16_t*)p.C + (int64_t)mb * p.ldc, rows && (LEAN || !p.c_skip) ? (uint32_t)(((int64_t)(rows - 1) * p.ldc + p.N) * 2) : 0);
   __amdgpu_buffer_rsrc_t xrs = crs;  // residual (BF16) / aux (GELU store, DGELU load)
   int64_t ldx = p.ldc;
   if constexpr (epi_bf16(EPI) && RES) {
     xrs = make_rsrc(p.resid + (int64_t)mb * p.ld_resid, rows ? (uint32_t)(((int64_t)(rows - 1) * p.ld_resid + p.N) * 2) : 0);
     ldx = p.ld_resid;
   } else if constexpr (EPI == EPI_GELU || EPI == EPI_DGELU) {
-    const bool has = p.aux != nullptr;
+    const bool has = (LN & LEAN_AUX) ? true : p.aux != nullptr;
     xrs = make_rsrc(has ? p.aux + (int64_t)mb * p.ld_aux : p.aux, has && rows ? (uint32_t)(((int64_t)(rows - 1) * p.ld_aux + p.N) * 2) : 0);
     ldx = p.ld_aux;
   }
-  const __amdgpu_buffer_rsrc_t brs = make_rsrc(p.bias, p.bias ? (uint32_t)p.N * 4 : 0);
+  const __amdgpu_buffer_rsrc_t brs = make_rsrc(p.bias, (LEAN ? L_BIAS : p.bias != nullptr) ? (uint32_t)p.N * 4 : 0);
   int c0[2];
   uint32_t vc[2], vx[2];
   float bias[2][8];
@@ -1064,7 +1072,7 @@ PVR_DEV void epilogue_direct(const GemmParams& p, v4f (&acc)[8][4], char* smem, 
     vx[jp] = okc ? (uint32_t)((li * ldx + c0[jp]) * 2) : OOB;
 #pragma unroll
     for (int e = 0; e < 8; ++e) bias[jp][e] = 0.f;
-    if constexpr (epi_bf16(EPI) || EPI == EPI_GELU) {
+    if constexpr ((epi_bf16(EPI) || EPI == EPI_GELU) && (!LEAN || (LN & LEAN_BIAS))) {
       const uint32_t vb = okc ? (uint32_t)(c0[jp] * 4) : OOB;
       const v4f b0 = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(brs, vb, 0, 0));
       const v4f b1 = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(brs, vb + 16, 0, 0));
@@ -1072,9 +1080,9 @@ PVR_DEV void epilogue_direct(const GemmParams& p, v4f (&acc)[8][4], char* smem, 
       for (int e = 0; e < 4; ++e) { bias[jp][e] = b0[e]; bias[jp][4 + e] = b1[e]; }
     }
   }
-  const uint64_t seed = (p.drop_thr ? *p.seed_ptr : 0ull) + p.seed_offset;
-  const uint32_t key = p.drop_thr ? rng_key(seed) : 0u;
-  const bool idx32 = (uint64_t)p.M * (uint64_t)p.N + 8 <= 0xFFFFFFFFull;
+  const uint64_t seed = ((LEAN ? L_DROP : p.drop_thr != 0) ? *p.seed_ptr : 0ull) + p.seed_offset;
+  const uint32_t key = (LEAN ? L_DROP : p.drop_thr != 0) ? rng_key(seed) : 0u;
+  const bool idx32 = LEAN ? true : (uint64_t)p.M * (uint64_t)p.N + 8 <= 0xFFFFFFFFull;
   // drop path (EPI_BF16_DP): the row factor is computed per fragment row inside the loop below (one
   // VGPR live next to the accumulators) from wave-uniform state
   DpRowScale dps{};
@@ -1108,7 +1116,7 @@ PVR_DEV void epilogue_direct(const GemmParams& p, v4f (&acc)[8][4], char* smem, 
   }
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
-    if (i == 1) stamp(p, 4);  // diagnostic builds only (p.dbg): row 0 done (bias / first inputs landed)
+    if (!LEAN && i == 1) stamp(p, 4);  // diagnostic builds only (p.dbg): row 0 done (bias / first inputs landed)
     const uint32_t so_c = (uint32_t)(i * 16 * (int)p.ldc * 2), so_x = (uint32_t)(i * 16 * (int)ldx * 2);
     const int m = mb + 16 * i + li;
     float rf = 1.f;
@@ -1134,7 +1142,7 @@ PVR_DEV void epilogue_direct(const GemmParams& p, v4f (&acc)[8][4], char* smem, 
       if constexpr (epi_bf16(EPI) || EPI == EPI_GELU) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] += bias[jp][e];
-        if (p.drop_thr) {
+        if (LEAN ? L_DROP : p.drop_thr != 0) {
           const uint64_t idx = (uint64_t)m * p.N + c0[jp];
           if (idx32) {
             bool k0[4], k1[4];
@@ -1155,7 +1163,7 @@ PVR_DEV void epilogue_direct(const GemmParams& p, v4f (&acc)[8][4], char* smem, 
           const float zero = rk ? 0.f : -0.f;
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = keep[e] && rk ? v[e] * rf : zero;
-        } else if (p.drop_thr) {
+        } else if (LEAN ? L_DROP : p.drop_thr != 0) {
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = keep[e] ? v[e] * p.drop_scale : 0.f;
         }
@@ -1181,7 +1189,7 @@ PVR_DEV void epilogue_direct(const GemmParams& p, v4f (&acc)[8][4], char* smem, 
           v[2 * q] = g2.x;  // the output (bf16 below, the fp8 copy)
           v[2 * q + 1] = g2.y;
         }
-        if (!p.c_skip) {  // uniform; c_skip: stored to a 0-byte range (the store count stays fixed)
+        if (LEAN || !p.c_skip) {  // uniform; c_skip: stored to a 0-byte range (the store count stays fixed)
 #pragma unroll
           for (int q = 0; q < 4; ++q) out[q] = pack2bf(v[2 * q], v[2 * q + 1]);
         } else {
@@ -1194,9 +1202,21 @@ PVR_DEV void epilogue_direct(const GemmParams& p, v4f (&acc)[8][4], char* smem, 
           v[2 * q] *= bf2f(xin[q] & 0xFFFF);
           v[2 * q + 1] *= bf2f(xin[q] >> 16);
         }
+        if constexpr (LEAN) {
+          // The general form rounds each product and then adds it to the column sum. With its c_skip
+          // branch gone the compiler would contract the two into one fused multiply-add here (other
+          // last bits in the sums): the products are made opaque so the add stays an add.
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            v2f t = {v[2 * q], v[2 * q + 1]};
+            asm volatile("" : "+v"(t));
+            v[2 * q] = t.x;
+            v[2 * q + 1] = t.y;
+          }
+        }
 #pragma unroll
         for (int e = 0; e < 8; ++e) csum[jp][e] += v[e];
-        if (!p.c_skip) {  // uniform; c_skip: stored to a 0-byte range (the store count stays fixed)
+        if (LEAN || !p.c_skip) {  // uniform; c_skip: stored to a 0-byte range (the store count stays fixed)
 #pragma unroll
           for (int q = 0; q < 4; ++q) out[q] = pack2bf(v[2 * q], v[2 * q + 1]);
         } else {
@@ -1218,7 +1238,7 @@ PVR_DEV void epilogue_direct(const GemmParams& p, v4f (&acc)[8][4], char* smem, 
       }
     }
   }
-  stamp(p, 5);  // every row's stores issued
+  if constexpr (!LEAN) stamp(p, 5);  // every row's stores issued
   if constexpr (EPI == EPI_DGELU) {
     {  // without colsum the atomics go to a 0-byte resource: the store count stays fixed
       // column sums over the wave's 128 rows (16 lanes of a row x 8 fragment rows: rows past M
@@ -1241,7 +1261,8 @@ PVR_DEV void epilogue_direct(const GemmParams& p, v4f (&acc)[8][4], char* smem, 
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();  // raw barrier: no vmcnt drain of the in-flight stores
       asm volatile("" ::: "memory");
-      const __amdgpu_buffer_rsrc_t srs = make_rsrc(p.colsum, p.colsum ? (uint32_t)p.N * 4 : 0);
+      const bool has_cs = (LN & LEAN_COLSUM) ? true : p.colsum != nullptr;
+      const __amdgpu_buffer_rsrc_t srs = make_rsrc(p.colsum, has_cs ? (uint32_t)p.N * 4 : 0);
       if (li == 0) {
         const int jp = wm;
         const uint32_t vo = c0[jp] < p.N ? (uint32_t)c0[jp] * 4 : OOB;
@@ -1476,11 +1497,15 @@ PVR_DEV void epilogue_staged(const GemmParams& p, v4f (&acc)[8][4], char* smem, 
 // release / acquire fences: a release writes back the XCD's whole L2, which with the GEMM's own
 // output dirty in it measured ~30 us per tail tile (profiles/r4/tail_ab.md).
 
+// The 32 fragments are summed one fragment row (4 fragments, 4 S loads) at a time, the rows kept
+// apart by a scheduling barrier: with every load of the tile free to move to the front, the
+// scheduler kept 2 S loads per fragment in flight next to the accumulators and spilled to scratch.
+// Each element is still slab 0 + slab 1 + ... in that order.
 template <int S>
 PVR_DEV void tail_sum(v4f (&acc)[8][4], __amdgpu_buffer_rsrc_t rs, int tid) {
   constexpr int SLAB_BYTES = 256 * 256 * 4;
 #pragma unroll
-  for (int i = 0; i < 8; ++i)
+  for (int i = 0; i < 8; ++i) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const uint32_t off = (uint32_t)(((i * 4 + j) * 512 + tid) * 16);
@@ -1490,6 +1515,8 @@ PVR_DEV void tail_sum(v4f (&acc)[8][4], __amdgpu_buffer_rsrc_t rs, int tid) {
         s += __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rs, off, q * SLAB_BYTES, CPOL_SC1));
       acc[i][j] = s;
     }
+    __builtin_amdgcn_sched_barrier(0);
+  }
 }
 
 PVR_DEV bool tail_gather(const GemmParams& p, v4f (&acc)[8][4], char* smem, int tloc, int tpart) {
@@ -1613,8 +1640,13 @@ PVR_DEV void splitk_fixup(const GemmParams& p, char* smem, int tile, int m0, int
   (void)smem;
 }
 
-template <bool AK, bool BKC, bool SWAP, int EPI, int ES = 2, int FA = 0, int FB = 0>
+// LN != 0: a lean instantiation (GemmLean bits, chosen by the host's lean_choose): no diagnostic
+// stamps, the split-tail code only with LEAN_TAIL, exactly one epilogue body with its options fixed.
+template <bool AK, bool BKC, bool SWAP, int EPI, int ES = 2, int FA = 0, int FB = 0, int LN = 0>
 __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(GemmParams p) {
+  constexpr bool LEAN = LN != 0;
+  constexpr bool TAIL = !LEAN || (LN & LEAN_TAIL) != 0;
+  static_assert(!LEAN || (ES == 2 && SWAP && AK && BKC && EPI == EPI_BF16), "lean list");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1630,17 +1662,23 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(GemmParams p) {
   // consecutive remapped ids (usually one XCD; a locality hint only, some tiles straddle two XCDs:
   // the sc1 partial stores / loads and the agent-scope arrival counter make the hand-off correct).
   int tt, kbeg, kend, tloc = 0, tpart = -1;
-  const TailPlan tp{p.tail_from, p.tail_split};
-  PVR_ASSERT((int)blockIdx.x < tail_grid(tp, ntm * ntn));
-  const TailUnit tu = tail_unit_c(tp, ntm * ntn, (int)blockIdx.x);
-  tt = tu.tile;
-  if (tu.part >= 0) {
-    tpart = tu.part;
-    tloc = tt - p.tail_from;
-    const int nkt = p.K / BKE;  // k-contiguous operands: K % BKE == 0 (host check)
-    kbeg = tail_kbeg(tpart, p.tail_split, nkt) * BKE;
-    kend = tail_kbeg(tpart + 1, p.tail_split, nkt) * BKE;
-  } else {
+  if constexpr (TAIL) {
+    const TailPlan tp{p.tail_from, p.tail_split};
+    PVR_ASSERT((int)blockIdx.x < tail_grid(tp, ntm * ntn));
+    const TailUnit tu = tail_unit_c(tp, ntm * ntn, (int)blockIdx.x);
+    tt = tu.tile;
+    if (tu.part >= 0) {
+      tpart = tu.part;
+      tloc = tt - p.tail_from;
+      const int nkt = p.K / BKE;  // k-contiguous operands: K % BKE == 0 (host check)
+      kbeg = tail_kbeg(tpart, p.tail_split, nkt) * BKE;
+      kend = tail_kbeg(tpart + 1, p.tail_split, nkt) * BKE;
+    } else {
+      kbeg = blockIdx.z * p.k_split_len;
+      kend = min(p.K, kbeg + p.k_split_len);
+    }
+  } else {  // no split tail in this launch (host): every workgroup owns one whole tile
+    tt = xcd_remap_c((int)blockIdx.x, ntm * ntn);
     kbeg = blockIdx.z * p.k_split_len;
     kend = min(p.K, kbeg + p.k_split_len);
   }
@@ -1694,7 +1732,7 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(GemmParams p) {
   v8s af[4][2], bf[2][2][2];
   PpStamps pst;
 
-  stamp(p, 0);
+  if constexpr (!LEAN) stamp(p, 0);
   // prologue: half-tiles 0..5 = all of K-tile 0, A0/B0 of K-tile 1
   pp_issue<0, AK, BKC, ES>(ars, brs, nul, smem, p.lda, p.ldb, 0, nk, wave, lane);
   pp_issue<1, AK, BKC, ES>(ars, brs, nul, smem, p.lda, p.ldb, 0, nk, wave, lane);
@@ -1705,7 +1743,7 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(GemmParams p) {
   asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // A0, B0 of K-tile 0 landed
   pp_barrier();
   if (wm == 1) pp_barrier();  // group 1 runs one barrier behind
-  stamp(p, 1);
+  if constexpr (!LEAN) stamp(p, 1);
   pst.begin();
 #ifdef PVR_GEMM_PHASE_STAMPS
   const uint64_t pst0 = pst.last;
@@ -1729,7 +1767,7 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(GemmParams p) {
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // null stages too: no LDS-DMA may outlive the workgroup
   if (wm == 0) pp_barrier();  // equal barrier counts for both groups
-  stamp(p, 2);
+  if constexpr (!LEAN) stamp(p, 2);
 #ifdef PVR_GEMM_PHASE_STAMPS
   pst.acc[7] = __builtin_amdgcn_s_memtime() - pst0;
   if (p.dbg && lane == 0) {
@@ -1738,10 +1776,12 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(GemmParams p) {
     for (int k = 0; k < 8; ++k) p.dbg[(b * 8 + wave) * 8 + k] = pst.acc[k];
   }
 #endif
-  if constexpr (epi_bf16(EPI) || EPI == EPI_GELU || EPI == EPI_DGELU) {
+  if constexpr (TAIL && (epi_bf16(EPI) || EPI == EPI_GELU || EPI == EPI_DGELU)) {
     if (tpart >= 0 && !tail_gather(p, acc, smem, tloc, tpart)) return;  // another part finishes the tile
   }
-  if constexpr (SWAP && (EPI == EPI_F32_ATOMIC || EPI == EPI_F32_STORE)) {
+  if constexpr (LEAN) {
+    epilogue_direct<EPI, (LN & LEAN_RES) != 0, false, LN>(p, acc, smem, m0 + wm * 128, n0 + wn * 64, wm, wn, lane);
+  } else if constexpr (SWAP && (EPI == EPI_F32_ATOMIC || EPI == EPI_F32_STORE)) {
     if ((p.N & 3) == 0 && !p.row_group)
       epilogue_staged<EPI, 128, false>(p, acc, smem, m0, n0, wm, wn, lane);
     else
@@ -1770,8 +1810,10 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(GemmParams p) {
   } else {
     epilogue<8, 4, SWAP, EPI>(p, acc, m0 + wm * 128, n0 + wn * 64, lane);
   }
-  if (p.dbg) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  stamp(p, 3);
+  if constexpr (!LEAN) {
+    if (p.dbg) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    stamp(p, 3);
+  }
 }
 
 // compute units of the current device (cached per device)
@@ -1806,6 +1848,26 @@ void plan_tail(GemmParams& q, int ntiles, int bke) {
   q.tail_split = t.split;
 }
 
+// Lean instantiations (gemm_lean.h) on / off: off, every launch takes the general kernel (A/B, tests).
+// g_lean_last: the GemmLean bits of the most recent pvr_gemm launch (0: a general kernel).
+bool g_gemm_lean = true;
+int g_lean_last = 0;
+
+template <bool AK, bool BKC, bool SWAP, int EPI, int ES, int FA, int FB, int LN>
+hipError_t launch_pp_as(const GemmParams& q, int grid, int nsplit, hipStream_t s) {
+  constexpr int SMEM = 2 * PP_BUF;
+  auto kern = gemm_pp_kernel<AK, BKC, SWAP, EPI, ES, FA, FB, LN>;
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
+    if (e != hipSuccess) return e;
+    attr_set = true;
+  }
+  g_lean_last = LN;
+  hipLaunchKernelGGL(kern, dim3(grid, 1, nsplit), dim3(512), SMEM, s, q);
+  return hipGetLastError();
+}
+
 template <bool AK, bool BKC, bool SWAP, int EPI, int ES = 2, int FA = 0, int FB = 0>
 hipError_t launch_pp(const GemmParams& p, hipStream_t s) {
   constexpr int SMEM = 2 * PP_BUF;
@@ -1825,6 +1887,14 @@ hipError_t launch_pp(const GemmParams& p, hipStream_t s) {
     if (nsplit == 1) {
       plan_tail(q, ntm * ntn, 128 / ES);
       grid = tail_grid(TailPlan{q.tail_from, q.tail_split}, ntm * ntn);
+    }
+  }
+  if constexpr (ES == 2 && SWAP && AK && BKC && EPI == EPI_BF16) {
+    constexpr int RBD = LEAN_ON | LEAN_BIAS | LEAN_RES | LEAN_DROP, T = LEAN_TAIL;
+    switch (g_gemm_lean ? lean_choose(q, LEAN_K_ONE_TILE, q.tail_split > 1) : 0) {
+      case RBD: return launch_pp_as<AK, BKC, SWAP, EPI, ES, FA, FB, RBD>(q, grid, nsplit, s);
+      case RBD | T: return launch_pp_as<AK, BKC, SWAP, EPI, ES, FA, FB, RBD | T>(q, grid, nsplit, s);
+      default: break;
     }
   }
   hipLaunchKernelGGL(kern, dim3(grid, 1, nsplit), dim3(512), SMEM, s, q);
@@ -1962,9 +2032,12 @@ PVR_DEV void ppp_phase(v4f (&acc)[8][4], v8s (&af)[4][2], v8s (&bf)[2][2][2], v8
 
 // ES = 1: fp8 operands (register-direct epilogue only; the GELU epilogue's e4m3 copy adds 16 stores
 // per wave beyond INFL, which only makes the counted waits retire more of them: still correct)
-template <bool SWAP, int EPI, bool DIRECT, int ES = 2, int FA = 0, int FB = 0>
+// LN != 0: a lean instantiation (GemmLean bits): no diagnostic stamps, one register-direct epilogue
+// body compiled with exactly the options the launch runs with.
+template <bool SWAP, int EPI, bool DIRECT, int ES = 2, int FA = 0, int FB = 0, int LN = 0>
 __global__ void __launch_bounds__(512, 2) gemm_ppp_kernel(GemmParams p) {
   static_assert(ES == 2 || DIRECT, "fp8 persistent GEMM: register-direct epilogue");
+  static_assert(LN == 0 || (ES == 2 && DIRECT && SWAP), "lean list");
   // epilogue stores per wave left in flight across the tile boundary (0: drain): the register-direct
   // BF16 epilogue issues 16 x 16 B, GELU 32 (output + derivative), dGELU 16 + 8 column-sum atomics
   // (to a 0-byte resource without colsum)
@@ -1998,7 +2071,7 @@ __global__ void __launch_bounds__(512, 2) gemm_ppp_kernel(GemmParams p) {
 
   // diagnostic stamps (p.dbg set, scripts/gemm_stamps.py --persistent): per workgroup, cycles in the
   // K loops and in the epilogues summed over its tiles, the whole kernel, and its tile count
-  const bool dstamp = p.dbg != nullptr;
+  const bool dstamp = LN ? false : p.dbg != nullptr;
   const uint64_t ts0 = dstamp ? __builtin_amdgcn_s_memtime() : 0;
   uint64_t ts_loop = 0, ts_epi = 0, ts_a = 0;
   int ntile_done = 0;
@@ -2043,7 +2116,9 @@ __global__ void __launch_bounds__(512, 2) gemm_ppp_kernel(GemmParams p) {
     // The next tile's first DMAs are in flight into the K-tile buffers; the epilogue works from
     // registers (DIRECT; the DGELU column-sum exchange uses the separate region) or stages in the
     // separate region behind them.
-    if constexpr (DIRECT) {
+    if constexpr (LN != 0) {
+      epilogue_direct<EPI, (LN & LEAN_RES) != 0, false, LN>(p, acc, smem + 2 * PP_BUF, cur.m0 + wm * 128, cur.n0 + wn * 64, wm, wn, lane);
+    } else if constexpr (DIRECT) {
       if (EPI == EPI_BF16_DP || (epi_bf16(EPI) && p.resid))  // (see gemm_pp_kernel: one instance per reachable epilogue)
         epilogue_direct<EPI, epi_bf16(EPI), ES == 1>(p, acc, smem + 2 * PP_BUF, cur.m0 + wm * 128, cur.n0 + wn * 64, wm, wn, lane);
       else
@@ -2096,6 +2171,24 @@ hipError_t launch_ppp(const GemmParams& p, hipStream_t s) {
   const int ntiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
   const int cus = device_cus();
   const int grid = ntiles < cus ? ntiles : cus;
+  if constexpr (ES == 2 && SWAP && (EPI == EPI_BF16 || EPI == EPI_GELU || EPI == EPI_DGELU)) {
+    // the one lean instantiation of this epilogue kind (gemm_lean.h)
+    constexpr int LN = EPI == EPI_BF16 ? (LEAN_ON | LEAN_BIAS)
+                       : EPI == EPI_GELU ? (LEAN_ON | LEAN_BIAS | LEAN_DROP | LEAN_AUX)
+                                         : (LEAN_ON | LEAN_AUX | LEAN_COLSUM);
+    if (g_gemm_lean && direct && lean_choose(p, LEAN_K_PERSISTENT, false) == LN) {
+      auto kl = gemm_ppp_kernel<SWAP, EPI, true, ES, FA, FB, LN>;
+      static bool lean_attr_set = false;
+      if (!lean_attr_set) {
+        hipError_t e = hipFuncSetAttribute((const void*)kl, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
+        if (e != hipSuccess) return e;
+        lean_attr_set = true;
+      }
+      g_lean_last = LN;
+      hipLaunchKernelGGL(kl, dim3(grid), dim3(512), SMEM, s, p);
+      return hipGetLastError();
+    }
+  }
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), SMEM, s, p);
   return hipGetLastError();
 }
@@ -2148,9 +2241,13 @@ extern "C" void pvr_set_fp8_persistent(int mode) { g_fp8_persistent = mode ? 1 :
 
 extern "C" int pvr_gemm_ws_takes(const pvr::GemmParams* pp) { return pvr_gemm_ws_ok(pp, pvr::device_cus()); }
 
+extern "C" void pvr_set_gemm_lean(int on) { pvr::g_gemm_lean = on != 0; }
+extern "C" int pvr_gemm_lean_last() { return pvr::g_lean_last; }
+
 extern "C" hipError_t pvr_gemm(const pvr::GemmParams* pp, hipStream_t s) {
   using namespace pvr;
   const GemmParams& p = *pp;
+  g_lean_last = 0;
   if (p.M <= 0 || p.N <= 0 || p.K <= 0) return hipSuccess;
   // compact class-token rows with the full tensor's dropout mask: the shared epilogue of the 128x128 tiles
   if (p.drop_row_mul && (p.drop_row_mul < 0 || p.tile_cfg != 0 || p.row_group || p.elem8)) return hipErrorInvalidValue;

@@ -169,6 +169,11 @@ hipError_t pvr_gemm(const pvr::GemmParams* p, hipStream_t s);
 // The split-K tail plan a one-tile-per-workgroup GEMM of this shape gets (0: none): tests / tools.
 int pvr_gemm_tail_split(int M, int N, int K, int elem_bytes, int max_units);
 void pvr_set_fp8_persistent(int mode);
+// Lean instantiations of the 256x256 ping-pong kernels (gemm_lean.h): 1 = a launch that matches the
+// list takes its lean kernel (default), 0 = every launch takes the general kernel (A/B, tests).
+void pvr_set_gemm_lean(int on);
+// GemmLean bits of the kernel the most recent pvr_gemm launched (0: a general kernel)
+int pvr_gemm_lean_last();
 // 1 if the wave-specialized kernel takes this GEMM (k-contiguous bf16 operands, bf16-output
 // epilogue without row remap / addend / fp8 copy, K a multiple of 64 and >= 256, 32-bit element
 // indices, 31-bit buffer offsets)

@@ -53,7 +53,32 @@ def key(demangled):
     return name.split()[-1], [t.strip() for t in targs.rstrip(">").split(",") if t.strip()]
 
 
+def same_kernel(kt, bt):
+    """bt is kt, or kt followed by template parameters the second file added at their defaults"""
+    return bt[:len(kt)] == kt and all(t in ("false", "0") for t in bt[len(kt):])
+
+
+def table(files):
+    """--table: per kernel of each file, its size and resources as one markdown table"""
+    for path in files:
+        ks = kernels(path)
+        dm = demangle(sorted(ks))
+        print(f"\n### {path}\n")
+        print("| kernel | instructions | conditional branches | VGPRs | private segment (B) |")
+        print("|---|---:|---:|---:|---:|")
+        for n in sorted(ks, key=lambda n: dm[n]):
+            kn, kt = key(dm[n])
+            body, res = ks[n]
+            ins = [l for l in body if not l.endswith(":")]
+            cbr = sum(1 for l in ins if l.split()[0].startswith("s_cbranch"))
+            print(f"| `{kn}<{','.join(kt)}>` | {len(ins)} | {cbr} | {res.get('.amdhsa_next_free_vgpr')} | "
+                  f"{res.get('.amdhsa_private_segment_fixed_size')} |")
+
+
 def main():
+    if sys.argv[1] == "--table":
+        table(sys.argv[2:])
+        return 0
     a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
     dm = demangle(sorted(set(a) | set(b)))
     bkeys = {n: key(dm[n]) for n in b}
@@ -62,7 +87,7 @@ def main():
     for pname in a:
         print(f"== {dm[pname]}")
         kn, kt = key(dm[pname])
-        name = next((n for n, (bn, bt) in bkeys.items() if bn == kn and bt == kt + ["false"] * (len(bt) - len(kt))), None)
+        name = next((n for n, (bn, bt) in bkeys.items() if bn == kn and same_kernel(kt, bt)), None)
         if name is None:
             print("   MISSING from the second file")
             missing += 1

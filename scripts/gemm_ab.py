@@ -5,10 +5,11 @@ optionally A/B'd over a switch of ours, interleaved in one process (rounds x var
 
   python scripts/gemm_ab.py                     # ViT-B/16 batch 256 (T = 50432)
   python scripts/gemm_ab.py --ab tail           # split-K tail of the last dispatch round on / off
+  python scripts/gemm_ab.py --ab lean           # lean instantiations on / off (general kernels)
   python scripts/gemm_ab.py --ab skfix --only wgrad   # weight gradients: in-launch split-K reduction on / off
   python scripts/gemm_ab.py --model vit_h14 --batch 256
 
-Prints one line per (GEMM, variant): median / min ms over the rounds, TFLOP/s, ratio vs hipBLASLt.
+Prints one line per (GEMM, variant): median [quartiles] (min .. max) ms over the rounds, TFLOP/s, ratio vs hipBLASLt.
 """
 from __future__ import annotations
 
@@ -84,6 +85,7 @@ def main():
     ap.add_argument("--model", default="vit_b16", choices=sorted(SHAPES))
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--rounds", type=int, default=4)
+    ap.add_argument("--iters", type=int, default=10, help="timed launches per round and variant")
     ap.add_argument("--ab", default="", help="'tail': split-K tail on / off")
     ap.add_argument("--only", default="", help="comma-separated substrings of case names")
     a = ap.parse_args()
@@ -95,6 +97,9 @@ def main():
     variants = [("", lambda: None)]
     if a.ab == "tail":
         variants = [("tail on ", lambda: ext.set_gemm_tail(True)), ("tail off", lambda: ext.set_gemm_tail(False))]
+    elif a.ab == "lean":
+        # lean instantiations (csrc/gemm_lean.h) vs the general kernels
+        variants = [("lean on ", lambda: ext.set_gemm_lean(True)), ("lean off", lambda: ext.set_gemm_lean(False))]
     elif a.ab == "skfix":
         # weight gradients: in-launch split-K reduction vs the separate reduce pass
         variants = [("skfix on", lambda: setattr(G, "SPLITK_FIXUP", True)), ("skfixoff", lambda: setattr(G, "SPLITK_FIXUP", False))]
@@ -114,19 +119,21 @@ def main():
                 res.setdefault((name, "lib"), []).append(timeit(lib))
             for vn, setv in order:
                 setv()
-                res.setdefault((name, vn), []).append(timeit(ours))
+                res.setdefault((name, vn), []).append(timeit(ours, iters=a.iters))
             if rnd % 2 == 0:
                 res.setdefault((name, "lib"), []).append(timeit(lib))
     ext.set_gemm_tail(True)
+    ext.set_gemm_lean(True)
     G.FORCE_TILE = None
-    print(f"# {a.model} batch {a.batch} (T = {T}), {a.rounds} rounds; median (min) ms, TFLOP/s at the median", flush=True)
+    print(f"# {a.model} batch {a.batch} (T = {T}), {a.rounds} rounds of {a.iters}; median [quartiles] (min .. max) ms, TFLOP/s at the median", flush=True)
     for name, fl, _, _ in cs:
         tl = statistics.median(res[(name, "lib")])
         print(f"{name:30s} hipBLASLt {tl:7.3f} ms {fl / tl / 1e9:7.1f} TF", flush=True)
         for vn, _ in variants:
             v = res[(name, vn)]
             t = statistics.median(v)
-            print(f"{name:30s} ours {vn:8s} {t:7.3f} ({min(v):7.3f}) ms {fl / t / 1e9:7.1f} TF  x{tl / t:5.2f} vs hipBLASLt",
+            q = statistics.quantiles(v, n=4) if len(v) >= 4 else [min(v), t, max(v)]
+            print(f"{name:30s} ours {vn:8s} {t:7.3f} [{q[0]:6.3f} {q[2]:6.3f}] ({min(v):7.3f} .. {max(v):7.3f}) ms {fl / t / 1e9:7.1f} TF  x{tl / t:5.2f} vs hipBLASLt",
                   flush=True)
 
 
