@@ -5,7 +5,8 @@
 //
 //   quant:  y = sat(x * qscale) in fp8,  amax = max(amax, max|x|)   (one pass; qscale == null:
 //           amax only, used to calibrate a tensor the first time it is seen / for weights)
-//   update: per tensor slot, push amax into a history ring, qscale = fmax / max(history) / 2^margin,
+//   update: per tensor slot, push amax into a history ring, qscale = fmax / max(history) / 2^margin
+//           (clamped to FLT_MAX where a tiny maximum overflows the quotient),
 //           dscale = 1 / qscale (the GEMM epilogue's dequant factor), reset amax; a non-finite
 //           amax is dropped (scales unchanged), so one overflowing step cannot poison the history
 #include "common.h"
@@ -248,7 +249,11 @@ __global__ void scale_update_kernel(float* __restrict__ hist, int H, unsigned* _
     m = fmaxf(m, h[k]);
   }
   h[0] = cur;
-  const float q = m > 0.f ? fmax[i] / m * margin_mul : 1.f;
+  // A finite window maximum below fmax / FLT_MAX (bf16 reaches 9e-41: an underflowing gradient
+  // tensor) overflows the quotient: qscale Inf, dscale 0, and the next quantize pass turns every zero
+  // element into 0 * Inf = NaN. Clamped to the largest finite float: every |x| <= m times it stays
+  // below fmax, and 0 * qscale stays 0.
+  const float q = m > 0.f ? fminf(fmax[i] / m * margin_mul, 3.402823466e+38f) : 1.f;
   qscale[i] = q;
   dscale[i] = 1.f / q;
 }

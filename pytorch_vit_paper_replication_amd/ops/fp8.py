@@ -22,6 +22,18 @@ Non-finite values: an Inf element makes its tensor's amax non-finite and a NaN e
 through the NaN-aware amax reduction (csrc/fp8.hip); the scale update then leaves that slot's
 history and scales unchanged, and FusedAdam's non-finite check skips the step.
 
+Numerics at the edges (pinned by ``tests/test_gpu_fp8_edges.py`` against the numpy model of
+``tests/fp8_reference.py``). Encode rule of every quantizing kernel: the float32 product ``x * qscale``
+is rounded to nearest even on the format's grid (subnormal spacing 2^-9 for e4m3, 2^-16 for e5m2);
+finite overflow and +-Inf saturate to +-max (448 / 57344, bytes 0x7E / 0x7B plus the sign); a NaN
+stays a NaN code (its sign is not defined); the sign of zero is kept. Products of bf16-subnormal
+inputs follow the device's denormal mode, which the project does not define. Scale clamp: for a
+finite window maximum ``m`` below ``fmax / FLT_MAX`` (about 1.3e-36 for e4m3, 1.7e-34 for e5m2; bf16
+reaches 9e-41) the quotient ``fmax / m`` overflows float32; ``qscale`` is then the largest finite
+float instead of Inf, so ``dscale`` stays positive, every ``|x| <= m`` times ``qscale`` stays below
+``fmax`` and ``0 * qscale`` stays 0 (an Inf scale turned every zero element into a NaN byte). For every
+finite ``m > 0`` both scales are finite and positive; ``m == 0`` gives 1.
+
 Data parallelism: the amax histories and scales stay per rank, with no cross-rank max. A scale only
 chooses how one rank's own activations / gradients are represented; every fp8 GEMM output is
 dequantized in its epilogue, so the weight gradients that enter the all-reduce are plain fp32 values,
