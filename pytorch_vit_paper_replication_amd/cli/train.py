@@ -85,6 +85,17 @@ def build_parser():
     p.add_argument("--mix-prob", type=float, default=1.0, help="probability that a batch is mixed")
     p.add_argument("--mix-switch-prob", type=float, default=0.5, help="with both: probability of CutMix over mixup")
     p.add_argument("--label-smoothing", type=float, default=0.0, metavar="E", help="label smoothing of the loss (0: off)")
+    p.add_argument("--bce-loss", action="store_true",
+                   help="binary cross-entropy (the sigmoid loss of DeiT-III) instead of softmax cross-entropy, against the "
+                        "same mixed / smoothed label rows; --label-smoothing is its smoothing")
+    p.add_argument("--bce-target-threshold", type=float, default=None, metavar="T",
+                   help="with --bce-loss: binarise the label rows, target = row > T (T in [0, 1); the recipes use 0.2)")
+    p.add_argument("--bce-sum-classes", action="store_true",
+                   help="with --bce-loss: sum the loss over the classes, then average over the batch (default: mean over both)")
+    p.add_argument("--head-bias-init", type=float, default=None, metavar="V",
+                   help="ViT: fill the classifier's bias with V before training. -log(C) for C classes is the usual choice "
+                        "for a sigmoid loss: each class then starts at probability 1 / (1 + C) instead of 1 / 2, so the "
+                        "first steps do not go into pushing C - 1 of C outputs down (default: the seeded initialisation)")
     p.add_argument("--random-erasing", type=float, default=0.0, metavar="P",
                    help="random erasing: erase one random box of each training image with this probability (0: off; "
                         "the DeiT recipe uses 0.25)")
@@ -110,6 +121,17 @@ def build_batch_mix(args, rank: int = 0):
                     label_smoothing=args.label_smoothing, generator=gen)
 
 
+def build_loss(args):
+    """The ``loss_fn`` of the run: ``nn.CrossEntropyLoss`` with ``--label-smoothing``, or with ``--bce-loss`` the
+    :class:`~..losses.BinaryCrossEntropy` of ``--label-smoothing`` / ``--bce-target-threshold`` / ``--bce-sum-classes``."""
+    if not args.bce_loss:
+        return torch.nn.CrossEntropyLoss(label_smoothing=args.label_smoothing)
+    from ..losses import BinaryCrossEntropy
+
+    return BinaryCrossEntropy(smoothing=args.label_smoothing, target_threshold=args.bce_target_threshold,
+                              sum_classes=args.bce_sum_classes)
+
+
 def build_random_erasing(args, rank: int = 0):
     """The :class:`~..data.random_erasing.RandomErasing` of ``--random-erasing`` (None when it is 0), its generator
     seeded from ``--seed`` per rank."""
@@ -133,11 +155,33 @@ def build_color_augment(args, rank: int = 0):
                         generator=gen)
 
 
+def build_model(args, ncls: int, rank: int = 0):
+    """The model of ``--model`` with ``ncls`` outputs and the options of the command line (on the CPU, before a
+    ``--resume`` loads into it)."""
+    from ..data import DeviceInput, RandomResizedCropFlip
+    from ..models import TinyVGG, vit
+
+    if args.model == "tinyvgg":
+        return TinyVGG(input_shape=3, hidden_units=args.hidden_units, output_shape=ncls)
+    drop = {} if args.dropout is None else dict(mlp_dropout=args.dropout, embedding_dropout=args.dropout)
+    model = vit(args.model, image_size=args.image_size, num_classes=ncls, drop_path=args.drop_path,
+                drop_path_schedule=args.drop_path_schedule, patch_dropout=args.patch_dropout, **drop)
+    if args.head_bias_init is not None:  # a --resume then loads the checkpoint's bias over it
+        model.init_head_bias(args.head_bias_init)
+    if args.dtype == "fp8":  # before a resume: the checkpoint's fp8 scaling state needs it
+        model.enable_fp8(wgrad=not args.fp8_bf16_wgrad, grad_fmt=args.fp8_grad)
+    if args.device_preprocess:
+        # per-rank crop draws: every rank augments its own shard differently (not saved by --resume)
+        gen = torch.Generator().manual_seed(args.seed * 1_000_003 + rank)
+        aug = RandomResizedCropFlip(generator=gen) if args.augment == "rrc-flip" else None
+        model.set_device_input(DeviceInput(augment=aug, color=build_color_augment(args, rank)))
+    return model
+
+
 def main(argv=None) -> int:
     from .. import engine
-    from ..data import DeviceInput, RandomResizedCropFlip, create_dataloaders, create_synthetic_dataloaders
+    from ..data import create_dataloaders, create_synthetic_dataloaders
     from ..data.transforms import default_vit_transform, uint8_transform
-    from ..models import TinyVGG, vit
     from ..optim import FusedAdam, FusedLamb, ModelEma, param_groups_weight_decay, warmup_linear_decay
     from ..parallel import DistributedDataParallel, init_distributed, is_dist
     from .. import _ext
@@ -171,6 +215,14 @@ def main(argv=None) -> int:
         raise SystemExit("--three-augment and --color-jitter need --device-preprocess")
     if not (args.color_jitter >= 0.0 and math.isfinite(args.color_jitter)):
         raise SystemExit("--color-jitter must be a finite value >= 0")
+    if not args.bce_loss and (args.bce_target_threshold is not None or args.bce_sum_classes):
+        raise SystemExit("--bce-target-threshold and --bce-sum-classes need --bce-loss")
+    if args.bce_target_threshold is not None and not 0.0 <= args.bce_target_threshold < 1.0:
+        raise SystemExit("--bce-target-threshold must be in [0, 1)")
+    if args.head_bias_init is not None and args.model == "tinyvgg":
+        raise SystemExit("--head-bias-init applies to the ViT models")
+    if args.head_bias_init is not None and not math.isfinite(args.head_bias_init):
+        raise SystemExit("--head-bias-init must be finite")
     src_size = args.source_size or args.image_size
     rank, world, device = init_distributed()
     set_seeds(args.seed)
@@ -184,19 +236,7 @@ def main(argv=None) -> int:
         train_dl, test_dl, class_names = create_dataloaders(args.train_dir, args.test_dir, tf, args.batch_size,
                                                             num_workers=args.num_workers)
     ncls = args.num_classes or len(class_names)
-    if args.model == "tinyvgg":
-        model = TinyVGG(input_shape=3, hidden_units=args.hidden_units, output_shape=ncls)
-    else:
-        drop = {} if args.dropout is None else dict(mlp_dropout=args.dropout, embedding_dropout=args.dropout)
-        model = vit(args.model, image_size=args.image_size, num_classes=ncls, drop_path=args.drop_path,
-                    drop_path_schedule=args.drop_path_schedule, patch_dropout=args.patch_dropout, **drop)
-        if args.dtype == "fp8":  # before a resume: the checkpoint's fp8 scaling state needs it
-            model.enable_fp8(wgrad=not args.fp8_bf16_wgrad, grad_fmt=args.fp8_grad)
-        if args.device_preprocess:
-            # per-rank crop draws: every rank augments its own shard differently (not saved by --resume)
-            gen = torch.Generator().manual_seed(args.seed * 1_000_003 + rank)
-            aug = RandomResizedCropFlip(generator=gen) if args.augment == "rrc-flip" else None
-            model.set_device_input(DeviceInput(augment=aug, color=build_color_augment(args, rank)))
+    model = build_model(args, ncls, rank)
     model.to(device)
     groups = param_groups_weight_decay(model, args.weight_decay)
     if args.optimizer == "lamb":
@@ -231,7 +271,7 @@ def main(argv=None) -> int:
            if is_dist() else model)
     with _ext.deterministic_mode() if args.deterministic else contextlib.nullcontext():
         engine.train(model=net, train_dataloader=train_dl, test_dataloader=test_dl, optimizer=opt,
-                     loss_fn=torch.nn.CrossEntropyLoss(label_smoothing=args.label_smoothing), lr_scheduler=sched,
+                     loss_fn=build_loss(args), lr_scheduler=sched,
                      epochs=args.epochs, device=device, max_grad_norm=args.max_grad_norm, checkpoint_dir=args.checkpoint_dir,
                      metrics_path=args.metrics, start_epoch=start_epoch, results=results,
                      batch_mix=build_batch_mix(args, rank), model_ema=ema, random_erasing=build_random_erasing(args, rank))

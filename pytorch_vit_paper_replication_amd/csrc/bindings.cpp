@@ -787,6 +787,51 @@ torch::Tensor xent_soft(torch::Tensor logits, torch::Tensor ya, torch::Tensor yb
   return loss;
 }
 
+// Binary cross-entropy with logits against xent_soft's target rows, binarised at thr when thr >= 0
+// (csrc/bce.hip bce_kernel): same outputs as xent_soft. sum_classes: the row loss sums over the classes
+// (timm), else it is their mean (BCEWithLogitsLoss); the kernel's row scale follows from it here, so
+// that it cannot disagree with C. Everything is checked before the first launch.
+torch::Tensor bce(torch::Tensor logits, torch::Tensor ya, torch::Tensor yb, torch::Tensor lam, double eps, double thr,
+                  bool sum_classes, c10::optional<torch::Tensor> dlogits, c10::optional<torch::Tensor> correct, double grad_scale,
+                  c10::optional<torch::Tensor> mean) {
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == torch::kFloat32, "bce: logits must be a float32 GPU tensor, got ",
+              logits.scalar_type());
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.size(1) >= 1, "bce: logits must be [B, C] row-major");
+  const int64_t B = logits.size(0), C = logits.size(1);
+  // (the kernel's column index advances by 1024 past C in an int)
+  TORCH_CHECK(B < (int64_t(1) << 31) && C < (int64_t(1) << 30) && (B <= 1 || logits.stride(0) >= C),
+              "bce: logits rows must not overlap, B must fit an int and C be below 2^30");
+  for (const torch::Tensor* y : {&ya, &yb})
+    TORCH_CHECK(y->is_cuda() && y->device() == logits.device() && y->scalar_type() == torch::kInt64 && y->is_contiguous() &&
+                    y->numel() == B,
+                "bce: ya / yb must be contiguous int64 [B] on the logits' device");
+  TORCH_CHECK(lam.device() == logits.device() && lam.scalar_type() == torch::kFloat32 && lam.is_contiguous() && lam.numel() == B,
+              "bce: lam must be contiguous float32 [B] on the logits' device");
+  TORCH_CHECK(eps >= 0.0 && eps <= 1.0, "bce: eps must be in [0, 1], got ", eps);
+  TORCH_CHECK(thr < 1.0, "bce: thr must be below 1 (negative: no threshold), got ", thr);
+  const bool has_dl = dlogits.has_value() && dlogits->defined(), has_corr = correct.has_value() && correct->defined();
+  const bool has_mean = mean.has_value() && mean->defined();
+  if (has_corr)
+    TORCH_CHECK(correct->is_cuda() && correct->device() == logits.device() && correct->is_contiguous() && correct->numel() >= B &&
+                    correct->scalar_type() == torch::kInt32,
+                "bce: correct int32 [B]");
+  if (has_dl)
+    TORCH_CHECK(dlogits->is_cuda() && dlogits->device() == logits.device() && dlogits->is_contiguous() && dlogits->numel() == B * C &&
+                    dlogits->scalar_type() == torch::kFloat32,
+                "bce: dlogits f32 [B][C]");
+  if (has_mean)
+    TORCH_CHECK(mean->is_cuda() && mean->device() == logits.device() && mean->scalar_type() == torch::kFloat32 && mean->numel() >= 1,
+                "bce: mean f32 [1]");
+  auto loss = torch::empty({B}, logits.options().dtype(torch::kFloat32));
+  const float row_scale = sum_classes ? 1.0f : 1.0f / (float)C;
+  check(pvr_bce(logits.data_ptr<float>(), logits.stride(0), ya.data_ptr<int64_t>(), yb.data_ptr<int64_t>(), lam.data_ptr<float>(),
+                (float)eps, thr >= 0.0 ? (float)thr : -1.0f, (int)B, (int)C, row_scale, loss.data_ptr<float>(), opt_ptr<float>(dlogits),
+                opt_ptr<int>(correct), (float)grad_scale, stream()),
+        "bce");
+  if (has_mean) check(pvr_mean(loss.data_ptr<float>(), (int)B, mean->data_ptr<float>(), stream()), "bce mean");
+  return loss;
+}
+
 void cls_rows(torch::Tensor cls, torch::Tensor pos, torch::Tensor out, int64_t B, int64_t D, int64_t row_stride,
               c10::optional<torch::Tensor> seed, int64_t seed_offset, double drop_p) {
   check(pvr_cls_rows(f32(cls, "cls"), f32(pos, "pos"), bf_mut(out, "out"), (int)B, (int)D, row_stride,
@@ -1642,6 +1687,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("mean") = py::none());
   m.def("xent_soft", &xent_soft, py::arg("logits"), py::arg("ya"), py::arg("yb"), py::arg("lam"), py::arg("eps"),
         py::arg("dlogits"), py::arg("correct"), py::arg("grad_scale"), py::arg("mean") = py::none());
+  m.def("bce", &bce, py::arg("logits"), py::arg("ya"), py::arg("yb"), py::arg("lam"), py::arg("eps"), py::arg("thr"),
+        py::arg("sum_classes"), py::arg("dlogits"), py::arg("correct"), py::arg("grad_scale"), py::arg("mean") = py::none());
   m.def("grad_norm", &grad_norm);
   m.def("norm_partial_blocks", []() { return pvr_norm_partial_blocks(); });
   m.def("adam", &adam, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("shadow"), py::arg("seg_start"),

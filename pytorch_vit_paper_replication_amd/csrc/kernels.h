@@ -279,6 +279,13 @@ hipError_t pvr_xent(const float* logits, int64_t ld, const int64_t* labels, int 
 hipError_t pvr_xent_soft(const float* logits, int64_t ld, const int64_t* ya, const int64_t* yb, const float* lam, float eps, int B,
                          int C, float* loss_rows, float* dlogits, int* correct, float grad_scale, hipStream_t s);
 
+// ---- bce.hip
+// Binary cross-entropy with logits against pvr_xent_soft's target rows q, or against q > thr when
+// thr >= 0 (thr < 0: off): loss_rows = row_scale * sum_c (log(1 + exp(x_c)) - x_c t_c), dlogits =
+// (sigmoid(x) - t) * grad_scale, correct = (argmax == ya). Invalid rows as in pvr_xent_soft.
+hipError_t pvr_bce(const float* logits, int64_t ld, const int64_t* ya, const int64_t* yb, const float* lam, float eps, float thr,
+                   int B, int C, float row_scale, float* loss_rows, float* dlogits, int* correct, float grad_scale, hipStream_t s);
+
 // ---- optim.hip
 int pvr_norm_partial_blocks();
 // workspace: NORM_BLOCKS floats. out: 3 floats.

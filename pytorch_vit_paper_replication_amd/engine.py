@@ -13,7 +13,8 @@ MI355X-oriented differences (no behaviour change):
     twice per batch (the reference's ``.item()`` calls, GM/engine.py:54,74,121,125);
   * with :class:`~..optim.FusedAdam` the clip runs inside the optimizer (device-side coefficient,
     no sync) and ``nn.CrossEntropyLoss()`` is executed by the fused softmax-xent kernel, whose
-    per-row argmax == label flags also give the accuracy (no separate argmax / eq / sum);
+    per-row argmax == label flags also give the accuracy (no separate argmax / eq / sum), as do those
+    of the fused sigmoid-loss kernel behind :class:`~.losses.BinaryCrossEntropy`;
   * under ``torch.distributed`` metrics are all-reduced across ranks and only rank 0 prints;
   * on a GPU the next batch's host->device copy runs on a copy stream while the current step
     computes (:class:`~.data.prefetch.DevicePrefetcher`, K17) instead of a blocking ``.to(device)``.
@@ -33,6 +34,7 @@ except Exception:  # pragma: no cover
         return x
 
 from .data.prefetch import prefetch
+from .losses import BinaryCrossEntropy
 from .ops import fused_vit
 from .ops.fused_vit import cross_entropy, soft_cross_entropy
 from .utils.profiling import range_push
@@ -55,6 +57,26 @@ class _SoftLoss:
 
     def __call__(self, logits, y):
         return soft_cross_entropy(logits, y, self.plan, self.label_smoothing)
+
+
+class _MixedBce:
+    """A :class:`~.losses.BinaryCrossEntropy` under ``batch_mix``: the module itself, called with the current
+    batch's plan (set per batch by ``train_step``) and with ``batch_mix.label_smoothing`` as its smoothing,
+    the rule cross-entropy has. A module that sets another non-zero smoothing of its own is refused."""
+
+    def __init__(self, module: BinaryCrossEntropy, label_smoothing: float):
+        eps = float(label_smoothing)
+        if module.smoothing != 0.0 and module.smoothing != eps:
+            raise ValueError(f"the loss's smoothing {module.smoothing} and batch_mix.label_smoothing {eps} differ: "
+                             "under batch_mix the smoothing is batch_mix.label_smoothing")
+        self.module, self.label_smoothing, self.plan = module, eps, None
+
+    def __call__(self, logits, y):
+        own, self.module.smoothing = self.module.smoothing, self.label_smoothing
+        try:
+            return self.module(logits, y, self.plan)
+        finally:
+            self.module.smoothing = own
 
 
 def _fused_loss(loss_fn):
@@ -84,7 +106,8 @@ def _accumulate(sums: torch.Tensor, loss: torch.Tensor, logits: torch.Tensor, y:
     """sums += [batch loss, batch accuracy] on the device. With the fused cross-entropy the kernel's
     per-row argmax == label flags are summed by one small HIP kernel; otherwise argmax / eq / sum."""
     with torch.no_grad():
-        corr = fused_vit.last_correct if lf is cross_entropy or isinstance(lf, _SoftLoss) else None
+        fused = lf is cross_entropy or isinstance(lf, (_SoftLoss, _MixedBce, BinaryCrossEntropy))
+        corr = fused_vit.last_correct if fused else None
         if corr is not None and sums.is_cuda and corr.numel() == logits.shape[0]:
             from . import _ext
 
@@ -136,8 +159,10 @@ def train_step(model: torch.nn.Module, dataloader, loss_fn: torch.nn.Module, opt
     ``batch_mix`` (optional :class:`~.data.batch_mix.BatchMix`): per batch a mixup / CutMix plan is drawn
     on the host and passed to the model (``model(X, mix=plan)``; a model whose ``forward`` has no ``mix``
     parameter gets ``mix_reference(X, plan)`` instead), and the loss is ``soft_cross_entropy`` with the
-    plan's label weights and ``batch_mix.label_smoothing`` in place of ``loss_fn``. The accuracy counts
-    ``argmax == y``, the samples' own labels.
+    plan's label weights and ``batch_mix.label_smoothing`` in place of ``loss_fn``. A
+    :class:`~.losses.BinaryCrossEntropy` ``loss_fn`` is kept instead: it is called with each batch's plan and
+    with ``batch_mix.label_smoothing`` as its smoothing (another non-zero smoothing of its own raises
+    ``ValueError``). The accuracy counts ``argmax == y``, the samples' own labels.
 
     ``random_erasing`` (optional :class:`~.data.random_erasing.RandomErasing`): per batch an erase plan is
     drawn on the host at the model's image size and passed to the model (``model(X, erase=plan)``, alone or
@@ -154,7 +179,12 @@ def train_step(model: torch.nn.Module, dataloader, loss_fn: torch.nn.Module, opt
     all-reduce times — without a host synchronisation per step."""
     _set_sampler_epoch(dataloader, epoch)
     model.train()
-    lf = _fused_loss(loss_fn) if batch_mix is None else _SoftLoss(batch_mix.label_smoothing)
+    if batch_mix is None:
+        lf = _fused_loss(loss_fn)
+    elif isinstance(loss_fn, BinaryCrossEntropy):
+        lf = _MixedBce(loss_fn, batch_mix.label_smoothing)
+    else:
+        lf = _SoftLoss(batch_mix.label_smoothing)
     takes_mix, mix_size = _mix_target(model) if batch_mix is not None else (False, None)
     takes_erase, erase_size = _mix_target(model, "erase") if random_erasing is not None else (False, None)
     sums = torch.zeros(2, dtype=torch.float32, device=device)

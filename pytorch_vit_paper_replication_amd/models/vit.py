@@ -304,6 +304,17 @@ class ViT(nn.Module):
         x = self.forward_features(x)
         return self.classifier(x[:, 0])
 
+    # ------------------------------------------------------------------ classifier bias
+    def init_head_bias(self, value: float) -> "ViT":
+        """Fill the classifier's bias with ``value`` (nothing else changes). For a sigmoid loss
+        (:class:`~..losses.BinaryCrossEntropy`) the usual choice is ``-log(C)``: every class then starts at
+        probability ``1 / (1 + C)`` instead of ``1 / 2``. The in-place write advances the parameter's version
+        counter, which is how the flat store sees any outside write: its bf16 shadow counts as stale and is
+        rebuilt before the next fused forward."""
+        with torch.no_grad():
+            self.classifier[0].bias.fill_(float(value))
+        return self
+
     # ------------------------------------------------------------------ stochastic depth
     def set_drop_path(self, rate: float, schedule: str = "linear") -> "ViT":
         """Stochastic depth (drop path; Huang et al. 2016, the DeiT / ViT from-scratch recipes): in training,

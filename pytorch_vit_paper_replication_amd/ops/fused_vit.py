@@ -854,6 +854,69 @@ def soft_cross_entropy(logits: torch.Tensor, target: torch.Tensor, plan=None, la
     return F.cross_entropy(logits, soft_targets(target, logits.shape[1], plan, eps, logits.dtype))
 
 
+class BinaryCrossEntropyFn(torch.autograd.Function):
+    """SoftCrossEntropyFn's counterpart for the sigmoid loss (csrc/bce.hip ``bce_kernel``): mean over the rows of
+    the binary cross-entropy against the same target rows, binarised at ``thr`` when ``thr >= 0``; the row loss is
+    the mean over the classes, or their sum with ``sum_classes``. ``correct`` flags ``argmax == ya``."""
+
+    @staticmethod
+    def forward(ctx, logits, ya, yb, lam, eps, thr, sum_classes, correct):
+        ext = _ext.ext()
+        lf = logits.float().contiguous()
+        B, C = lf.shape
+        dl = torch.empty_like(lf) if logits.requires_grad else None
+        mean = torch.empty((), dtype=torch.float32, device=lf.device)
+        ext.bce(lf, ya, yb, lam, eps, thr, sum_classes, dl, correct, 1.0 / B if sum_classes else 1.0 / (B * C), mean.view(1))
+        ctx.save_for_backward(dl) if dl is not None else None
+        ctx.in_dtype = logits.dtype
+        return mean
+
+    @staticmethod
+    def backward(ctx, g):
+        (dl,) = ctx.saved_tensors
+        return (_ext.ext().scale_by(dl, g.float().reshape(1).contiguous()).to(ctx.in_dtype),) + (None,) * 7
+
+
+def binary_cross_entropy(logits: torch.Tensor, target: torch.Tensor, plan=None, label_smoothing: float = 0.0,
+                         target_threshold: Optional[float] = None, sum_classes: bool = False) -> torch.Tensor:
+    """Binary cross-entropy with logits against the target rows of :func:`soft_cross_entropy` (integer labels
+    ``target`` ``[B]``, mixed by ``plan``, smoothed by ``label_smoothing``): the loss of DeiT-III and of timm's
+    ``--bce-loss``. ``target_threshold`` (optional, below 1) binarises the rows, ``t = q > threshold``.
+    The result is ``F.binary_cross_entropy_with_logits``'s ``mean`` over ``[B, C]``, or with ``sum_classes``
+    the sum over the classes averaged over the batch. On the GPU one fused kernel (loss, gradient, and the
+    ``last_correct`` flags ``argmax == y_b``); elsewhere the torch function on the explicit rows."""
+    global last_correct
+    eps = float(label_smoothing)
+    if plan is not None and plan.batch != logits.shape[0]:
+        raise ValueError(f"binary_cross_entropy: a plan for {plan.batch} samples with {logits.shape[0]} logit rows")
+    if target_threshold is not None and not 0.0 <= target_threshold < 1.0:
+        raise ValueError(f"binary_cross_entropy: target_threshold must be in [0, 1), got {target_threshold}")
+    if _ext.use_fused(logits) and logits.dim() == 2 and target.dim() == 1:
+        B, dev = logits.shape[0], logits.device
+        ya = target.long().contiguous()
+        if plan is None:
+            yb = ya
+            lam = _ONES.get((dev, B))
+            if lam is None:
+                with torch.inference_mode(False):  # kept across calls: not an inference tensor
+                    lam = _ONES[(dev, B)] = torch.ones(B, dtype=torch.float32, device=dev)
+        else:
+            _, partner, lam = plan.on(dev)
+            yb = ya.index_select(0, partner)
+        correct = torch.empty(B, dtype=torch.int32, device=dev)
+        thr = -1.0 if target_threshold is None else float(target_threshold)
+        loss = BinaryCrossEntropyFn.apply(logits, ya, yb, lam, eps, thr, bool(sum_classes), correct)
+        last_correct = correct
+        return loss
+    last_correct = None
+    t = soft_targets(target, logits.shape[1], plan, eps, logits.dtype)
+    if target_threshold is not None:
+        t = t.gt(target_threshold).to(t.dtype)
+    if sum_classes:
+        return F.binary_cross_entropy_with_logits(logits, t, reduction="none").sum(-1).mean()
+    return F.binary_cross_entropy_with_logits(logits, t)
+
+
 _UNIT: dict = {}
 
 
