@@ -1,11 +1,10 @@
 // Memory-bound helper kernels (16-B vector accesses throughout, SURVEY.md K1-K4, K11 bias-grad):
 //   * flat fp32 -> bf16 shadow cast of the parameter store
 //   * bias-gradient column sums, optionally fused with the dropout-mask backward
-//   * patch embedding: im2col gather (fp32 image -> bf16 patch rows), CLS rows, and the backward
-//     reduction of the embedding-dropout / position-embedding / CLS gradients;
+//   * patch embedding: CLS rows, and the backward reduction of the embedding-dropout / position-embedding /
+//     CLS gradients (the im2col gather of the forward is patchify.hip);
 //   * patch dropout: the per-sample keep table (ranks of counter-hash keys), the gathered position
-//     addend, and the KEEP instantiations of the patchify kernels and of the backward's first pass;
-//   * random erasing: the ERASE instantiations of the patchify kernels and the fill's noise as a kernel.
+//     addend, and the KEEP instantiation of the backward's first pass.
 #include "common.h"
 #include "kernels.h"
 
@@ -212,458 +211,6 @@ __global__ void __launch_bounds__(256) pos_gather_kernel(const float* __restrict
     const int64_t b = r / (n_keep + 1);
     const int src = n == 0 ? 0 : min(max(keep[b * n_keep + n - 1], 0), np - 1) + 1;
     ((float4*)out)[i] = ((const float4*)pos)[(int64_t)src * d4 + c];
-  }
-}
-
-// One mixed pixel of the patchify kernels' MIX variants (MixRow in kernels.h): fp32, contraction off
-PVR_DEV float mix_value(float own, float par, bool inside, float lam, float oml) {
-#pragma clang fp contract(off)
-  return inside ? par : lam == 1.f ? own : lam * own + oml * par;
-}
-
-// mix[b] with the partner index made safe to use (the host validates the plan it was given; a device
-// tensor that differs from it must still never index outside the batch)
-PVR_DEV MixRow mix_row(const MixRow* __restrict__ mix, int b, int B) {
-  const int4 lo = ((const int4*)(mix + b))[0], hi = ((const int4*)(mix + b))[1];
-  MixRow r;
-  r.partner = (unsigned)lo.x < (unsigned)B ? lo.x : b;
-  r.lam = __int_as_float(lo.y);
-  r.bx0 = lo.z; r.by0 = lo.w; r.bx1 = hi.x; r.by1 = hi.y;
-  return r;
-}
-
-// a[c] of a by-value kernel argument without a divergent index into the argument segment
-PVR_DEV float pick4(const float (&a)[4], int c) { return c == 0 ? a[0] : c == 1 ? a[1] : c == 2 ? a[2] : a[3]; }
-
-// Random erasing (EraseRow / EraseArgs in kernels.h). The "pixel" fill of element e at site seed sd: a
-// standard normal by Box-Muller from two hashes of the dropout counter. u1 = ((h1 >> 8) + 1) * 2^-24 lies
-// in (0, 1] and u2 = (h2 >> 8) * 2^-24 in [0, 1), both exact in fp32, so |z| <= sqrt(2 * 24 * ln 2) = 5.77.
-// fp32, contraction off, every operation rounded on its own. The patchify kernels and
-// erase_noise_kernel call this one function, so the tests' host replay sees the kernels' bits.
-PVR_DEV float erase_normal(uint64_t sd, uint64_t e) {
-#pragma clang fp contract(off)
-  const uint32_t h1 = rng_hash(sd, 2 * e), h2 = rng_hash(sd, 2 * e + 1);
-  const float u1 = (float)((h1 >> 8) + 1u) * 5.9604644775390625e-08f;
-  const float u2 = (float)(h2 >> 8) * 5.9604644775390625e-08f;
-  return sqrtf(-2.0f * logf(u1)) * cosf(6.2831853f * u2);
-}
-
-// The fill of pixel (s, c, y, x) of a [.][C][H][W] model image (sd: *er.seed + er.offset in ERASE_PIXEL mode)
-PVR_DEV float erase_fill(const EraseArgs& er, uint64_t sd, int s, int c, int y, int x, int C, int H, int W) {
-  if (er.mode == ERASE_PIXEL) return erase_normal(sd, (((uint64_t)s * C + c) * H + y) * W + x);
-  return pick4(er.value, c);
-}
-
-PVR_DEV bool erase_hit(const EraseRow& e, int x, int y) { return x >= e.x0 && x < e.x1 && y >= e.y0 && y < e.y1; }
-
-PVR_DEV EraseRow erase_row(const EraseRow* __restrict__ rows, int b) {
-  const int4 q = *(const int4*)(rows + b);
-  return EraseRow{q.x, q.y, q.z, q.w};
-}
-
-// The mix row of an ERASE kernel: without a plan the identity (partner = self, lam == 1, empty box), under
-// which mix_value selects the sample's own value and no partner pixel is read
-PVR_DEV MixRow erase_mix_row(const MixRow* __restrict__ mix, int b, int B) {
-  if (mix) return mix_row(mix, b, B);
-  MixRow r;
-  r.partner = b; r.lam = 1.f;
-  r.bx0 = r.by0 = r.bx1 = r.by1 = 0;
-  return r;
-}
-
-__global__ void __launch_bounds__(256) erase_noise_kernel(const uint64_t* seed_ptr, uint64_t off, float* __restrict__ out, int64_t n) {
-  const uint64_t sd = *seed_ptr + off;
-  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) out[i] = erase_normal(sd, (uint64_t)i);
-}
-
-// img [B][C][H][W] fp32 -> patches [B*np][Kp] bf16, k = (c*P + ph)*P + pw, zero padded to Kp.
-// One thread per 8 consecutive k of a patch row: with P % 8 == 0 they are 8 consecutive pixels of
-// one image row (two float4 loads, one 16-B store); the zero padding past C*P*P and other patch
-// sizes (P = 14) take the per-element path.
-// MIX: sample b's pixels are blended with / replaced by those of sample mix[b].partner while they
-// are gathered (mixup / CutMix, see MixRow in kernels.h). A pixel whose weight is 0 or 1 is read from
-// one sample only, so CutMix moves the bytes of the plain gather; mixup reads the input twice.
-// KEEP (patch dropout, both patchify kernels): only n_keep patches per sample are gathered. Output row r
-// belongs to sample r / n_keep and holds patch keep[r] of it (keep [B][n_keep] int32, ascending per
-// sample: patch_keep_kernel); the pixels, the padding and the mix plan (a box is in image pixels) are
-// those of that patch in the plain kernel.
-// ERASE (random erasing, both patchify kernels; only with MIX, whose plan may then be null = identity): a
-// sample's own value inside its erase box er.rows[sample] is the fill (erase_fill) instead of the pixel,
-// before the mix formula: the own and the partner pixel each test their own sample's box. An erased
-// pixel is not loaded (eight erased pixels of the vector path load nothing); the loads that remain are
-// those of the MIX kernel, inside the image. C <= 4 (the fill's per-channel value; host-checked).
-// The fills of a thread's 8 pixels stay unrolled (16 call sites per code shape, 8 - 12 k instructions per
-// instantiation): one rolled loop over the erased pixels is a third of the code but measured 10 % slower,
-// a thread's fills then running one after the other (profiles/random_erasing/).
-template <bool MIX, bool KEEP = false, bool ERASE = false>
-__global__ void __launch_bounds__(256) im2col_kernel(const float* __restrict__ img, uint16_t* __restrict__ out,
-                                                      int B, int C, int H, int W, int P, int Kp,
-                                                      const MixRow* __restrict__ mix, const int* __restrict__ keep, int n_keep,
-                                                      EraseArgs er) {
-  static_assert(MIX || !ERASE, "ERASE exists only together with MIX");
-  uint64_t esd = 0;
-  if constexpr (ERASE) {
-    if (er.mode == ERASE_PIXEL) esd = *er.seed + er.offset;
-  }
-  const int gw = W / P, np = (H / P) * gw;
-  const int kc = C * P * P, k8 = Kp / 8;
-  const bool vec = (P % 8 == 0) && (W % 4 == 0);
-  const int64_t total = (int64_t)B * (KEEP ? n_keep : np) * k8;
-  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int k0 = (int)(i % k8) * 8;
-    const int64_t rowi = i / k8;
-    const int pidx = KEEP ? min(max(keep[rowi], 0), np - 1) : (int)(rowi % np);
-    const int b = (int)(rowi / (KEEP ? n_keep : np));
-    const int y0 = (pidx / gw) * P, x0 = (pidx % gw) * P;
-    float v[8];
-    if constexpr (MIX) {
-      const MixRow r = ERASE ? erase_mix_row(mix, b, B) : mix_row(mix, b, B);
-      const float oml = 1.0f - r.lam;
-      EraseRow eo = {0, 0, 0, 0}, ep = eo;  // the own and the partner sample's erase box
-      if constexpr (ERASE) {
-        eo = erase_row(er.rows, b);
-        ep = erase_row(er.rows, r.partner);
-      }
-      if (vec && k0 + 8 <= kc) {
-        const int c = k0 / (P * P), rem = k0 % (P * P), ph = rem / P, pw = rem % P;
-        const int y = y0 + ph, x = x0 + pw;
-        const bool yin = y >= r.by0 && y < r.by1;
-        bool in[8];
-        int n_in = 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          in[j] = yin && x + j >= r.bx0 && x + j < r.bx1;
-          n_in += in[j];
-        }
-        const int64_t off = ((int64_t)c * H + y) * W + x;
-        float4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, p0 = a0, p1 = a0;
-        if constexpr (ERASE) {
-          bool ea[8], eq[8], need_a = false, need_p = false;  // the own / the partner pixel is used and erased
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const bool use_p = in[j] || r.lam != 1.f;
-            ea[j] = !in[j] && erase_hit(eo, x + j, y);
-            eq[j] = use_p && erase_hit(ep, x + j, y);
-            need_a |= !in[j] && !ea[j];
-            need_p |= use_p && !eq[j];
-          }
-          if (need_a) {
-            const float* src = img + (int64_t)b * C * H * W + off;
-            a0 = *(const float4*)src; a1 = *(const float4*)(src + 4);
-          }
-          if (need_p) {
-            const float* src = img + (int64_t)r.partner * C * H * W + off;
-            p0 = *(const float4*)src; p1 = *(const float4*)(src + 4);
-          }
-          const float a[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-          const float p[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const float fa = ea[j] ? erase_fill(er, esd, b, c, y, x + j, C, H, W) : a[j];
-            const float fp = eq[j] ? erase_fill(er, esd, r.partner, c, y, x + j, C, H, W) : p[j];
-            v[j] = mix_value(fa, fp, in[j], r.lam, oml);
-          }
-        } else {
-          if (n_in < 8) {
-            const float* src = img + (int64_t)b * C * H * W + off;
-            a0 = *(const float4*)src; a1 = *(const float4*)(src + 4);
-          }
-          if (n_in > 0 || r.lam != 1.f) {
-            const float* src = img + (int64_t)r.partner * C * H * W + off;
-            p0 = *(const float4*)src; p1 = *(const float4*)(src + 4);
-          }
-          const float a[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-          const float p[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = mix_value(a[j], p[j], in[j], r.lam, oml);
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int k = k0 + j;
-          v[j] = 0.f;
-          if (k < kc) {
-            const int c = k / (P * P), rem = k % (P * P), ph = rem / P, pw = rem % P;
-            const int y = y0 + ph, x = x0 + pw;
-            const bool in = y >= r.by0 && y < r.by1 && x >= r.bx0 && x < r.bx1;
-            const int64_t off = ((int64_t)c * H + y) * W + x;
-            float a = 0.f, p = 0.f;
-            if constexpr (ERASE) {
-              if (!in) a = erase_hit(eo, x, y) ? erase_fill(er, esd, b, c, y, x, C, H, W) : img[(int64_t)b * C * H * W + off];
-              if (in || r.lam != 1.f)
-                p = erase_hit(ep, x, y) ? erase_fill(er, esd, r.partner, c, y, x, C, H, W) : img[(int64_t)r.partner * C * H * W + off];
-            } else {
-              if (!in) a = img[(int64_t)b * C * H * W + off];
-              if (in || r.lam != 1.f) p = img[(int64_t)r.partner * C * H * W + off];
-            }
-            v[j] = mix_value(a, p, in, r.lam, oml);
-          }
-        }
-      }
-    } else if (vec && k0 + 8 <= kc) {
-      const int c = k0 / (P * P), rem = k0 % (P * P), ph = rem / P, pw = rem % P;
-      const float* src = img + (((int64_t)b * C + c) * H + y0 + ph) * W + x0 + pw;
-      const float4 a = *(const float4*)src, bq = *(const float4*)(src + 4);
-      v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = bq.x; v[5] = bq.y; v[6] = bq.z; v[7] = bq.w;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int k = k0 + j;
-        v[j] = 0.f;
-        if (k < kc) {
-          const int c = k / (P * P), rem = k % (P * P), ph = rem / P, pw = rem % P;
-          v[j] = img[(((int64_t)b * C + c) * H + y0 + ph) * W + x0 + pw];
-        }
-      }
-    }
-    uint4 o;
-    o.x = pack2bf(v[0], v[1]); o.y = pack2bf(v[2], v[3]); o.z = pack2bf(v[4], v[5]); o.w = pack2bf(v[6], v[7]);
-    *(uint4*)(out + rowi * Kp + k0) = o;
-  }
-}
-
-// uint8 source image -> the same bf16 patch rows as im2col_kernel, with the input pipeline's
-// per-image work fused in: scale to [0,1], per-channel normalise and (GEOM) a per-sample crop box
-// resampled bilinearly to H x W, flipped when the box runs right to left.
-//   img  [B][C <= 4][Hs][Ws] uint8 by element strides (sb, sc, sy, sx): contiguous NCHW and
-//        channels_last are both read in place
-//   geom [B][4] = (x0, y0, x1, y1) in source pixel-edge coordinates, x0 > x1 = flipped
-// All arithmetic is fp32 in the order of the PyTorch reference (data/device_input.py
-// preprocess_reference), every operation rounded on its own: contraction is off in this
-// kernel, and the two divisions of ((p / 255) - mean) / std are correctly rounded (hipcc's default;
-// a multiply by 1/255 differs from the division in the last bit for 126 of the 256 byte values).
-// Without GEOM (Hs == H, Ws == W) and with `vec` (host-checked: sx == 1, P % 8 == 0, base and every
-// other stride 8-byte aligned) the 8 pixels of a thread are one 8-byte load; otherwise per element.
-struct U8Norm {
-  float mean[4], stdv[4];
-};
-
-PVR_DEV float u8_normalise(float p, float mean, float stdv) {
-#pragma clang fp contract(off)
-  return (p / 255.0f - mean) / stdv;
-}
-
-// Source coordinate of output index o along one axis: box start e0, step = (e1 - e0) / n_out;
-// returns the two taps i <= j (both inside [0, n_src - 1] for any e0 / step, NaN included) and the weight of j.
-PVR_DEV void u8_axis(int o, float e0, float step, int n_src, int& i, int& j, float& w) {
-#pragma clang fp contract(off)
-  float s = e0 + ((float)o + 0.5f) * step - 0.5f;
-  s = fminf(fmaxf(s, 0.f), (float)(n_src - 1));  // fmaxf(NaN, 0) = 0
-  const float f = floorf(s);
-  i = min(max((int)f, 0), n_src - 1);
-  j = min(i + 1, n_src - 1);
-  w = s - f;
-}
-
-// Output pixel (x, y) of one channel plane under crop box g (steps precomputed): the bilinear sample
-// of the four taps, normalised; fp32, before the bf16 cast. The GEOM loop body of im2col_u8_kernel as
-// a function, for its MIX variant, which samples two images per pixel (the no-mix kernel keeps the
-// body inline: calling this there schedules differently).
-PVR_DEV float u8_sample(const uint8_t* src_c, int64_t sy, int64_t sx, const float4& g, float stepx, float stepy, int x, int y,
-                        int Ws, int Hs, float mean, float stdv) {
-#pragma clang fp contract(off)
-  int xi, xj, yi, yj;
-  float wx, wy;
-  u8_axis(x, g.x, stepx, Ws, xi, xj, wx);
-  u8_axis(y, g.y, stepy, Hs, yi, yj, wy);
-  const float ta = (float)src_c[yi * sy + xi * sx], tb = (float)src_c[yi * sy + xj * sx];
-  const float tc = (float)src_c[yj * sy + xi * sx], td = (float)src_c[yj * sy + xj * sx];
-  const float top = ta + wx * (tb - ta), bot = tc + wx * (td - tc);
-  return u8_normalise(top + wy * (bot - top), mean, stdv);
-}
-
-// MIX (see im2col_kernel): the blend runs on the normalised fp32 values, each sample under its own
-// crop box, so the no-GEOM table then holds fp32 values instead of their bf16 roundings.
-// KEEP: as in im2col_kernel.
-// ERASE: as in im2col_kernel; the fill replaces the normalised value.
-template <bool GEOM, bool MIX, bool KEEP = false, bool ERASE = false>
-__global__ void __launch_bounds__(256) im2col_u8_kernel(const uint8_t* __restrict__ img, int64_t sb, int64_t sc, int64_t sy,
-                                                         int64_t sx, U8Norm nrm, const float* __restrict__ geom,
-                                                         uint16_t* __restrict__ out, int B, int C, int Hs, int Ws, int H, int W,
-                                                         int P, int Kp, int vec, const MixRow* __restrict__ mix,
-                                                         const int* __restrict__ keep, int n_keep, EraseArgs er) {
-#pragma clang fp contract(off)
-  static_assert(MIX || !ERASE, "ERASE exists only together with MIX");
-  uint64_t esd = 0;
-  if constexpr (ERASE) {
-    if (er.mode == ERASE_PIXEL) esd = *er.seed + er.offset;
-  }
-  // Without GEOM a pixel is one of 256 byte values: each block tabulates the normalised bf16 of every
-  // (channel, byte) pair once, with the same operations and hence the same bits, and its loop does
-  // no division. Two correctly rounded divisions per element make the kernel ALU-bound: 51 us
-  // against 38 us with the table at 256 x 224 x 224 (the float kernel: 43 us), profiles/input_u8/.
-  __shared__ uint16_t lut[GEOM || MIX ? 1 : 4][256];
-  __shared__ float lutf[!GEOM && MIX ? 4 : 1][256];
-  if constexpr (!GEOM && MIX) {
-    for (int c = 0; c < C; ++c) lutf[c][threadIdx.x] = u8_normalise((float)threadIdx.x, nrm.mean[c], nrm.stdv[c]);
-    __syncthreads();
-  } else if constexpr (!GEOM) {
-    for (int c = 0; c < C; ++c) lut[c][threadIdx.x] = f2bf(u8_normalise((float)threadIdx.x, nrm.mean[c], nrm.stdv[c]));
-    __syncthreads();
-  }
-  const int gw = W / P, np = (H / P) * gw;
-  const int kc = C * P * P, k8 = Kp / 8;
-  const int64_t total = (int64_t)B * (KEEP ? n_keep : np) * k8;
-  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int k0 = (int)(i % k8) * 8;
-    const int64_t rowi = i / k8;
-    const int pidx = KEEP ? min(max(keep[rowi], 0), np - 1) : (int)(rowi % np);
-    const int b = (int)(rowi / (KEEP ? n_keep : np));
-    const int py = (pidx / gw) * P, px = (pidx % gw) * P;
-    const uint8_t* src_b = img + b * sb;
-    uint32_t h[8];  // bf16 bits
-    if constexpr (MIX) {
-      const MixRow r = ERASE ? erase_mix_row(mix, b, B) : mix_row(mix, b, B);
-      const float oml = 1.0f - r.lam;
-      const uint8_t* src_p = img + r.partner * sb;
-      float v[8];
-      EraseRow eo = {0, 0, 0, 0}, ep = eo;  // the own and the partner sample's erase box
-      if constexpr (ERASE) {
-        eo = erase_row(er.rows, b);
-        ep = erase_row(er.rows, r.partner);
-      }
-      if constexpr (!GEOM) {
-        if (vec && k0 + 8 <= kc) {
-          const int c = k0 / (P * P), rem = k0 % (P * P), ph = rem / P, pw = rem % P;
-          const int y = py + ph, x = px + pw;
-          const bool yin = y >= r.by0 && y < r.by1;
-          bool in[8];
-          int n_in = 0;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            in[j] = yin && x + j >= r.bx0 && x + j < r.bx1;
-            n_in += in[j];
-          }
-          const int64_t off = c * sc + (int64_t)y * sy + x;
-          uint2 qa = {0u, 0u}, qp = {0u, 0u};
-          if constexpr (ERASE) {
-            bool ea[8], eq[8], need_a = false, need_p = false;  // the own / the partner pixel is used and erased
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-              const bool use_p = in[j] || r.lam != 1.f;
-              ea[j] = !in[j] && erase_hit(eo, x + j, y);
-              eq[j] = use_p && erase_hit(ep, x + j, y);
-              need_a |= !in[j] && !ea[j];
-              need_p |= use_p && !eq[j];
-            }
-            if (need_a) qa = *(const uint2*)(src_b + off);
-            if (need_p) qp = *(const uint2*)(src_p + off);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-              const uint32_t a = ((j < 4 ? qa.x : qa.y) >> (8 * (j & 3))) & 0xFFu;
-              const uint32_t p = ((j < 4 ? qp.x : qp.y) >> (8 * (j & 3))) & 0xFFu;
-              const float fa = ea[j] ? erase_fill(er, esd, b, c, y, x + j, C, H, W) : lutf[c][a];
-              const float fp = eq[j] ? erase_fill(er, esd, r.partner, c, y, x + j, C, H, W) : lutf[c][p];
-              v[j] = mix_value(fa, fp, in[j], r.lam, oml);
-            }
-          } else {
-            if (n_in < 8) qa = *(const uint2*)(src_b + off);
-            if (n_in > 0 || r.lam != 1.f) qp = *(const uint2*)(src_p + off);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-              const uint32_t a = ((j < 4 ? qa.x : qa.y) >> (8 * (j & 3))) & 0xFFu;
-              const uint32_t p = ((j < 4 ? qp.x : qp.y) >> (8 * (j & 3))) & 0xFFu;
-              v[j] = mix_value(lutf[c][a], lutf[c][p], in[j], r.lam, oml);
-            }
-          }
-        } else {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const int k = k0 + j;
-            v[j] = 0.f;
-            if (k < kc) {
-              const int c = k / (P * P), rem = k % (P * P), ph = rem / P, pw = rem % P;
-              const int y = py + ph, x = px + pw;
-              const bool in = y >= r.by0 && y < r.by1 && x >= r.bx0 && x < r.bx1;
-              const int64_t off = c * sc + (int64_t)y * sy + (int64_t)x * sx;
-              float a = 0.f, p = 0.f;
-              if constexpr (ERASE) {
-                if (!in) a = erase_hit(eo, x, y) ? erase_fill(er, esd, b, c, y, x, C, H, W) : lutf[c][src_b[off]];
-                if (in || r.lam != 1.f) p = erase_hit(ep, x, y) ? erase_fill(er, esd, r.partner, c, y, x, C, H, W) : lutf[c][src_p[off]];
-              } else {
-                if (!in) a = lutf[c][src_b[off]];
-                if (in || r.lam != 1.f) p = lutf[c][src_p[off]];
-              }
-              v[j] = mix_value(a, p, in, r.lam, oml);
-            }
-          }
-        }
-      } else {
-        // each sample under its own crop box
-        const float4 g = *(const float4*)(geom + (int64_t)b * 4), gp = *(const float4*)(geom + (int64_t)r.partner * 4);
-        const float stepx = (g.z - g.x) / (float)W, stepy = (g.w - g.y) / (float)H;
-        const float pstepx = (gp.z - gp.x) / (float)W, pstepy = (gp.w - gp.y) / (float)H;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int k = k0 + j;
-          v[j] = 0.f;
-          if (k < kc) {
-            const int c = k / (P * P), rem = k % (P * P), ph = rem / P, pw = rem % P;
-            const int y = py + ph, x = px + pw;
-            const bool in = y >= r.by0 && y < r.by1 && x >= r.bx0 && x < r.bx1;
-            const float mean = pick4(nrm.mean, c), stdv = pick4(nrm.stdv, c);
-            float a = 0.f, p = 0.f;
-            if constexpr (ERASE) {
-              if (!in)
-                a = erase_hit(eo, x, y) ? erase_fill(er, esd, b, c, y, x, C, H, W)
-                                        : u8_sample(src_b + c * sc, sy, sx, g, stepx, stepy, x, y, Ws, Hs, mean, stdv);
-              if (in || r.lam != 1.f)
-                p = erase_hit(ep, x, y) ? erase_fill(er, esd, r.partner, c, y, x, C, H, W)
-                                        : u8_sample(src_p + c * sc, sy, sx, gp, pstepx, pstepy, x, y, Ws, Hs, mean, stdv);
-            } else {
-              if (!in) a = u8_sample(src_b + c * sc, sy, sx, g, stepx, stepy, x, y, Ws, Hs, mean, stdv);
-              if (in || r.lam != 1.f) p = u8_sample(src_p + c * sc, sy, sx, gp, pstepx, pstepy, x, y, Ws, Hs, mean, stdv);
-            }
-            v[j] = mix_value(a, p, in, r.lam, oml);
-          }
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) h[j] = f2bf(v[j]);
-    } else if constexpr (!GEOM) {
-      if (vec && k0 + 8 <= kc) {
-        const int c = k0 / (P * P), rem = k0 % (P * P), ph = rem / P, pw = rem % P;
-        const uint2 q = *(const uint2*)(src_b + c * sc + (int64_t)(py + ph) * sy + px + pw);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          h[j] = lut[c][(q.x >> (8 * j)) & 0xFFu];
-          h[4 + j] = lut[c][(q.y >> (8 * j)) & 0xFFu];
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int k = k0 + j;
-          h[j] = 0;
-          if (k < kc) {
-            const int c = k / (P * P), rem = k % (P * P), ph = rem / P, pw = rem % P;
-            h[j] = lut[c][src_b[c * sc + (int64_t)(py + ph) * sy + (int64_t)(px + pw) * sx]];
-          }
-        }
-      }
-    } else {
-      const float4 g = *(const float4*)(geom + (int64_t)b * 4);
-      const float stepx = (g.z - g.x) / (float)W, stepy = (g.w - g.y) / (float)H;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int k = k0 + j;
-        h[j] = 0;
-        if (k < kc) {
-          const int c = k / (P * P), rem = k % (P * P), ph = rem / P, pw = rem % P;
-          const uint8_t* src_c = src_b + c * sc;
-          int xi, xj, yi, yj;
-          float wx, wy;
-          u8_axis(px + pw, g.x, stepx, Ws, xi, xj, wx);
-          u8_axis(py + ph, g.y, stepy, Hs, yi, yj, wy);
-          const float ta = (float)src_c[yi * sy + xi * sx], tb = (float)src_c[yi * sy + xj * sx];
-          const float tc = (float)src_c[yj * sy + xi * sx], td = (float)src_c[yj * sy + xj * sx];
-          const float top = ta + wx * (tb - ta), bot = tc + wx * (td - tc);
-          h[j] = f2bf(u8_normalise(top + wy * (bot - top), pick4(nrm.mean, c), pick4(nrm.stdv, c)));
-        }
-      }
-    }
-    uint4 o;
-    o.x = h[0] | (h[1] << 16); o.y = h[2] | (h[3] << 16); o.z = h[4] | (h[5] << 16); o.w = h[6] | (h[7] << 16);
-    *(uint4*)(out + rowi * Kp + k0) = o;
   }
 }
 
@@ -1062,74 +609,6 @@ extern "C" hipError_t pvr_pos_gather(const float* pos, const int* keep, float* o
   int64_t blocks = (total + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(pos_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, s, pos, keep, out, B, np, n_keep, D);
-  return hipGetLastError();
-}
-
-// an erase argument the kernels can take: an aligned table, a known mode, a seed in pixel mode, C <= 4
-static bool erase_args_ok(const pvr::EraseArgs& e, int C) {
-  if (!e.rows) return true;
-  if (reinterpret_cast<uintptr_t>(e.rows) % 16 || C < 1 || C > 4) return false;
-  return e.mode == pvr::ERASE_CONST || (e.mode == pvr::ERASE_PIXEL && e.seed);
-}
-
-extern "C" hipError_t pvr_erase_noise(const uint64_t* seed, uint64_t offset, float* out, int64_t n, hipStream_t s) {
-  using namespace pvr;
-  if (!seed || !out || n < 0) return hipErrorInvalidValue;
-  if (n == 0) return hipSuccess;
-  int64_t blocks = (n + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(erase_noise_kernel, dim3((unsigned)blocks), dim3(256), 0, s, seed, offset, out, n);
-  return hipGetLastError();
-}
-
-extern "C" hipError_t pvr_im2col(const float* img, uint16_t* out, int B, int C, int H, int W, int P, int Kp,
-                                 const pvr::MixRow* mix, const int* keep, int n_keep, pvr::EraseArgs erase, hipStream_t s) {
-  using namespace pvr;
-  if (Kp % 8 || (mix && reinterpret_cast<uintptr_t>(mix) % 16)) return hipErrorInvalidValue;
-  if (!erase_args_ok(erase, C)) return hipErrorInvalidValue;
-  const int np = (H / P) * (W / P);
-  if (keep && (n_keep < 1 || n_keep > np)) return hipErrorInvalidValue;
-  const int64_t total = (int64_t)B * (keep ? n_keep : np) * (Kp / 8);
-  if (total <= 0) return hipSuccess;
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  const auto kern = erase.rows ? (keep ? im2col_kernel<true, true, true> : im2col_kernel<true, false, true>)
-                    : keep     ? (mix ? im2col_kernel<true, true> : im2col_kernel<false, true>)
-                               : (mix ? im2col_kernel<true> : im2col_kernel<false>);
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, s, img, out, B, C, H, W, P, Kp, mix, keep, keep ? n_keep : 0, erase);
-  return hipGetLastError();
-}
-
-extern "C" hipError_t pvr_im2col_u8(const uint8_t* img, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float* mean,
-                                    const float* stdv, const float* geom, uint16_t* out, int B, int C, int Hs, int Ws, int H,
-                                    int W, int P, int Kp, int vec, const pvr::MixRow* mix, const int* keep, int n_keep,
-                                    pvr::EraseArgs erase, hipStream_t s) {
-  using namespace pvr;
-  if (mix && reinterpret_cast<uintptr_t>(mix) % 16) return hipErrorInvalidValue;
-  if (!erase_args_ok(erase, C)) return hipErrorInvalidValue;
-  if (Kp % 8 || P <= 0 || C < 1 || C > 4 || H % P || W % P || Kp < C * P * P || Hs < 1 || Ws < 1) return hipErrorInvalidValue;
-  if (!geom && (Hs != H || Ws != W)) return hipErrorInvalidValue;
-  if (vec && (geom || sx != 1 || P % 8 || reinterpret_cast<uintptr_t>(img) % 8 || sb % 8 || sc % 8 || sy % 8))
-    return hipErrorInvalidValue;
-  if (keep && (n_keep < 1 || n_keep > (H / P) * (W / P))) return hipErrorInvalidValue;
-  const int64_t total = (int64_t)B * (keep ? n_keep : (H / P) * (W / P)) * (Kp / 8);
-  if (total <= 0) return hipSuccess;
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > 2048) blocks = 2048;  // 8 blocks per CU: a block's 256 x C table entries serve ~9 trips of its threads at b256
-  U8Norm nrm;
-  for (int c = 0; c < 4; ++c) {
-    nrm.mean[c] = c < C ? mean[c] : 0.f;
-    nrm.stdv[c] = c < C ? stdv[c] : 1.f;
-  }
-  const auto kern =
-      erase.rows ? (keep ? (geom ? im2col_u8_kernel<true, true, true, true> : im2col_u8_kernel<false, true, true, true>)
-                         : (geom ? im2col_u8_kernel<true, true, false, true> : im2col_u8_kernel<false, true, false, true>))
-      : keep     ? (mix ? (geom ? im2col_u8_kernel<true, true, true> : im2col_u8_kernel<false, true, true>)
-                        : (geom ? im2col_u8_kernel<true, false, true> : im2col_u8_kernel<false, false, true>))
-                 : (mix ? (geom ? im2col_u8_kernel<true, true> : im2col_u8_kernel<false, true>)
-                        : (geom ? im2col_u8_kernel<true, false> : im2col_u8_kernel<false, false>));
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, s, img, sb, sc, sy, sx, nrm, geom, out, B, C, Hs, Ws, H, W, P, Kp,
-                     vec, mix, keep, keep ? n_keep : 0, erase);
   return hipGetLastError();
 }
 

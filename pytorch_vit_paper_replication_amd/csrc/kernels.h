@@ -86,7 +86,7 @@ struct EraseRow {
 static_assert(sizeof(EraseRow) == 16, "EraseRow is one int32 [4] row of the erase table");
 
 // The fill: value[c] per channel (ERASE_CONST, the model's normalised space), or a standard normal
-// per element from the counter hash (ERASE_PIXEL): erase_normal(*seed + offset, e) of elementwise.hip
+// per element from the counter hash (ERASE_PIXEL): erase_normal(*seed + offset, e) of patchify.hip
 // with e = ((s * C + c) * H + y) * W + x, the element's index in the model image.
 constexpr int ERASE_CONST = 0, ERASE_PIXEL = 1;
 // The patchify kernels' erase argument. rows null: no erasing (the kernels that ran before it existed).
@@ -226,6 +226,7 @@ hipError_t pvr_patch_keep(const uint64_t* seed, uint64_t offset, int B, int np, 
 // out f32 [B][n_keep + 1][D]: row 1 + s of sample b = pos[keep[b][s] + 1], row 0 = pos[0] (pos [np + 1][D]; D % 4 == 0,
 // 16-byte aligned bases): the embedding GEMM's position addend under patch dropout
 hipError_t pvr_pos_gather(const float* pos, const int* keep, float* out, int B, int np, int n_keep, int D, hipStream_t s);
+// The patchify kernels and the erase fill's noise (patchify.hip).
 // mix (both patchify kernels; null: none): the batch's MixRow plan, host-validated (bindings.cpp mix_rows).
 // keep (both; null: every patch): pvr_patch_keep's table; out then has B * n_keep rows, row r = patch
 // keep[r] of sample r / n_keep

@@ -11,7 +11,7 @@ pixel ``(b, c, y, x)`` is::
 
 in fp32, every operation rounded on its own. Mixup is ``lam < 1`` with an empty box, CutMix ``lam == 1``
 with a box. On the fused GPU path the patch-embedding kernels do this while they gather the patch
-rows (``csrc/elementwise.hip``, ``MIX`` variants): CutMix moves the bytes of an unmixed batch, mixup
+rows (``csrc/patchify.hip``, ``MIX`` variants): CutMix moves the bytes of an unmixed batch, mixup
 reads the input a second time; nothing downstream changes. Elsewhere (CPU, ``PVR_DISABLE_FUSED=1``)
 :func:`mix_reference` runs the same formula as torch ops.
 

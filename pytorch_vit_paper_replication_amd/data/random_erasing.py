@@ -14,7 +14,7 @@ untouched. ``fill`` is ``value[c]`` (mode ``"const"``; 0 is the mean colour afte
 normal per element (mode ``"pixel"``).
 
 On the fused GPU path the patch-embedding kernels do this while they gather the patch rows
-(``csrc/elementwise.hip``, ``ERASE`` variants): an erased pixel is not loaded, and the normal comes from the
+(``csrc/patchify.hip``, ``ERASE`` variants): an erased pixel is not loaded, and the normal comes from the
 counter hash of the dropout masks at site ``ERASE_SITE`` (``ext.erase_noise`` returns the same values).
 Elsewhere (CPU, ``PVR_DISABLE_FUSED=1``) :func:`erase_reference` runs the formula as torch ops and draws
 the normal from torch's RNG.

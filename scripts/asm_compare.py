@@ -1,6 +1,7 @@
 """Compare two hipcc -S outputs of one source file, kernel by kernel:
 
     python scripts/asm_compare.py parent.s new.s
+    python scripts/asm_compare.py parent.s new_a.s,new_b.s    (a side may be several files: kernels that moved)
 
 For every kernel of the first file: whether the second has it, and whether its instruction stream
 (labels normalised, comments dropped) and its resources (.amdhsa_* lines: registers, LDS, scratch,
@@ -79,7 +80,7 @@ def main():
     if sys.argv[1] == "--table":
         table(sys.argv[2:])
         return 0
-    a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+    a, b = ({n: k for path in side.split(",") for n, k in kernels(path).items()} for side in sys.argv[1:3])
     dm = demangle(sorted(set(a) | set(b)))
     bkeys = {n: key(dm[n]) for n in b}
     missing = 0

@@ -1,5 +1,5 @@
 """Host oracles of random erasing, shared by tests/test_random_erasing_cpu.py and
-tests/test_gpu_random_erasing.py: the "pixel" fill of csrc/elementwise.hip ``erase_normal`` in numpy (float64,
+tests/test_gpu_random_erasing.py: the "pixel" fill of csrc/patchify.hip ``erase_normal`` in numpy (float64,
 and the same formula in float32 as the yardstick of a kernel checked against float64), built on the hash
 replica of tests/test_drop_path_cpu.py, and the erase formula one sample at a time."""
 import numpy as np
