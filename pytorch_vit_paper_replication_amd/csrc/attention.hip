@@ -260,7 +260,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) a
                 fast ? pack4_fp8_direct<0>(v0, v1, v2, v3) : (uint32_t)pack2_fp8<0, true>(v2, v3, pack2_fp8<0, false>(v0, v1, 0));
           }
         }
-        if (g == 0 && live) lse[(int64_t)bh * N + q] = (m_run[gi] + __log2f(l)) * LN2;
+        if (g == 0 && live) lse[(int64_t)bh * N + q] = lse_nat_log2(m_run[gi], l);
       }
       continue;
     }
@@ -285,7 +285,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) a
               (uint32_t)pack2_fp8<0, true>(v[2] * qs, v[3] * qs, pack2_fp8<0, false>(v[0] * qs, v[1] * qs, 0));
         }
       }
-      if (g == 0) lse[(int64_t)bh * N + q] = (m_run[gi] + __log2f(l)) * LN2;
+      if (g == 0) lse[(int64_t)bh * N + q] = lse_nat_log2(m_run[gi], l);
     }
   }
   if (staged) {  // LDS images -> whole-row 16-B chunks (each wave reads back only its own region)
@@ -388,7 +388,7 @@ __global__ void __launch_bounds__(((NF + QF - 1) / QF) * 64) attn_fwd_head_kerne
       __builtin_amdgcn_raw_buffer_store_b64(w, rs, vo + 32 * e, 0, 0);
     }
     const __amdgpu_buffer_rsrc_t ls = make_rsrc(lse + (int64_t)pr * N, (uint32_t)N * 4);
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint((m + __log2f(l)) * LN2), ls,
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(lse_nat_log2(m, l)), ls,
                                           ok && g == 0 ? (uint32_t)q * 4 : 0x80000000u, 0, 0);
   };
 
@@ -845,12 +845,16 @@ __global__ void __launch_bounds__(512) attn_bwd_kernel(const uint16_t* __restric
       }
     }
     // dS^T -> LDS (bf16) [key_local][32 queries]: the packed dK-product operands sf, four
-    // consecutive queries per 8-B write (a = 0: queries 4g.., a = 1: 16 + 4g..)
+    // consecutive queries per 8-B write (a = 0: queries 4g.., a = 1: 16 + 4g..).
+    // Keys past N (the padding of the block's last wave with a key) are written as zero: their K
+    // fragment is zero, so S = 0 and P = exp2(-lse log2e), which is inf once lse < -88 nat (every score
+    // of the row far below 0). Their dK / dV are never stored, but dS = +-inf would meet the zero K rows
+    // of the dQ product as inf * 0 = NaN in every dQ row of the block.
     {
       typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 #pragma unroll
       for (int f = 0; f < 2; ++f) {
-        const v4u w = __builtin_bit_cast(v4u, sf[f]);
+        const v4u w = kw0 + 16 * f + li < N ? __builtin_bit_cast(v4u, sf[f]) : v4u{0u, 0u, 0u, 0u};
         *(__attribute__((address_space(3))) v2u*)(dsw + dsw0 + 1024 * f) = v2u{w[0], w[1]};
         *(__attribute__((address_space(3))) v2u*)(dsw + dsw1 + 1024 * f) = v2u{w[2], w[3]};
       }
@@ -2145,7 +2149,7 @@ __global__ void __launch_bounds__(256) attn_cls_fwd_kernel(const uint16_t* __res
     l += pk;
   }
   l = cls_block_reduce<false>(l, r4);  // (its barriers also publish the probabilities)
-  if (tid == 0) lse[bh] = m + logf(l);
+  if (tid == 0) lse[bh] = lse_nat(m, l);
   float acc[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) acc[j] = 0.f;

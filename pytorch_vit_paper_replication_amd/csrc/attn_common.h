@@ -16,6 +16,47 @@ struct Hd {
 };
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float LN2 = 0.6931471805599453f;
+constexpr float LN2_LO = -1.9046543e-9f;  // ln 2 - LN2
+
+// Log-sum-exp in nats, x + ln l for a normaliser l > 0, to about half an ulp of the result.
+// (m2 + __log2f(l)) * LN2 rounds three times at the size of the result (v_log's ulp at log2 l ~ 8, the
+// sum, the product): up to 1.2e-6 at lse = log N ~ 6, more than a row of small scores can afford
+// (|lse - ref| <= 4e-7 max(1, max |score|), tests/test_gpu_attn_regimes.py). Here l = f 2^e with f in
+// [sqrt(1/2), sqrt(2)), so v_log sees |log2 f| <= 1/2 (its error ~6e-8 absolute); the sum with e and
+// the product with ln 2 = LN2 + LN2_LO are carried as exact two-term sums (no multiply is contracted
+// into them), and the result is rounded once. ~20 VALU per query, once per kernel.
+PVR_DEV float two_sum(float a, float b, float& err) {
+#pragma clang fp contract(off)
+  const float s = a + b, bb = s - a;
+  err = (a - (s - bb)) + (b - bb);
+  return s;
+}
+PVR_DEV void log2_split(float l, float& e, float& lf) {
+  float f = __builtin_amdgcn_frexp_mantf(l);  // [1/2, 1)
+  int ei = __builtin_amdgcn_frexp_expf(l);
+  if (f < 0.70710678f) { f *= 2.f; ei -= 1; }
+  e = (float)ei;
+  lf = __log2f(f);
+}
+// m2: the running max in scaled log2 units -> (m2 + log2 l) ln 2
+PVR_DEV float lse_nat_log2(float m2, float l) {
+#pragma clang fp contract(off)
+  float e, lf, err;
+  log2_split(l, e, lf);
+  const float s = two_sum(m2, e, err);
+  const float p = s * LN2;
+  return p + __builtin_fmaf(s, LN2_LO, __builtin_fmaf(err + lf, LN2, __builtin_fmaf(s, LN2, -p)));
+}
+// m: the max in nats -> m + ln l
+PVR_DEV float lse_nat(float m, float l) {
+#pragma clang fp contract(off)
+  float e, lf, err;
+  log2_split(l, e, lf);
+  const float a = e * LN2;  // ln l = a + al
+  const float al = __builtin_fmaf(e, LN2_LO, __builtin_fmaf(lf, LN2, __builtin_fmaf(e, LN2, -a)));
+  const float s = two_sum(m, a, err);
+  return s + (err + al);
+}
 
 // XOR on the 16-B chunk index of 128-B rows: conflict-free for row reads (ds_read_b128, 16 rows x
 // one chunk), and for transposed reads of rows {4g+q, 16+4g+q} and {8g+q, 8g+4+q}.
