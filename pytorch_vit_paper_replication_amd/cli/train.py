@@ -64,6 +64,9 @@ def build_parser():
     p.add_argument("--patch-dropout", type=float, default=0.0, metavar="RATE",
                    help="ViT: train on a random subset of each image's patch tokens, dropping this fraction "
                         "(0: off; evaluation sees every patch; not with --dtype fp8)")
+    p.add_argument("--layer-scale", type=float, default=None, metavar="INIT",
+                   help="ViT: LayerScale, a learnable per-channel scale on each residual branch, initialised to INIT "
+                        "(DeiT-III: 1e-4; default: off; not with --dtype fp8)")
     p.add_argument("--deterministic", action="store_true",
                    help="fixed-order reductions instead of float atomics: bitwise-repeatable gradients")
     p.add_argument("--bucket-mb", type=float, default=28.0, help="DDP gradient bucket size (MiB)")
@@ -165,7 +168,7 @@ def build_model(args, ncls: int, rank: int = 0):
         return TinyVGG(input_shape=3, hidden_units=args.hidden_units, output_shape=ncls)
     drop = {} if args.dropout is None else dict(mlp_dropout=args.dropout, embedding_dropout=args.dropout)
     model = vit(args.model, image_size=args.image_size, num_classes=ncls, drop_path=args.drop_path,
-                drop_path_schedule=args.drop_path_schedule, patch_dropout=args.patch_dropout, **drop)
+                drop_path_schedule=args.drop_path_schedule, patch_dropout=args.patch_dropout, layer_scale=args.layer_scale, **drop)
     if args.head_bias_init is not None:  # a --resume then loads the checkpoint's bias over it
         model.init_head_bias(args.head_bias_init)
     if args.dtype == "fp8":  # before a resume: the checkpoint's fp8 scaling state needs it
@@ -201,6 +204,10 @@ def main(argv=None) -> int:
         raise SystemExit("--patch-dropout applies to the ViT models")
     if args.patch_dropout and args.dtype == "fp8":
         raise SystemExit("--patch-dropout does not combine with --dtype fp8")
+    if args.layer_scale is not None and args.model == "tinyvgg":
+        raise SystemExit("--layer-scale applies to the ViT models")
+    if args.layer_scale is not None and args.dtype == "fp8":
+        raise SystemExit("--layer-scale does not combine with --dtype fp8")
     if not 0.0 <= args.patch_dropout < 1.0:
         raise SystemExit("--patch-dropout must be in [0, 1)")
     if not 0.0 <= args.random_erasing <= 1.0:
@@ -266,6 +273,9 @@ def main(argv=None) -> int:
             was, now = saved.get("patch_dropout", 0.0), cfg.get("patch_dropout", 0.0)
             if was != now:
                 print(f"[INFO] The run continues with --patch-dropout {now}; the checkpoint was written with {was}")
+            if ("layer_scale" in saved) != ("layer_scale" in cfg):  # (load_state_dict has then already named the keys)
+                print(f"[INFO] --layer-scale is {'on' if 'layer_scale' in cfg else 'off'}; the checkpoint was written with it "
+                      f"{'on' if 'layer_scale' in saved else 'off'}")
     net = (DistributedDataParallel(model, bucket_cap_mb=args.bucket_mb,
                                    comm_dtype=torch.bfloat16 if args.comm_dtype == "bf16" else None)
            if is_dist() else model)

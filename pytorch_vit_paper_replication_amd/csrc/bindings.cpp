@@ -1206,6 +1206,80 @@ void zero_f32(torch::Tensor x) {
   check(pvr_zero_f32(f32_mut(x, "x"), x.numel(), stream()), "zero_f32");
 }
 
+// LayerScale fold (csrc/layerscale.hip): meta int64 [n][8] on the GPU with meta_host, the same rows on the
+// host, which are what is validated here: every matrix, scale and bias inside `master`, every output
+// inside w16 / wt16 / bhat, R, C and the offsets multiples of 8, the tile prefixes those of the rows.
+void layerscale_fold(torch::Tensor master, torch::Tensor w16, torch::Tensor wt16, torch::Tensor bhat, torch::Tensor meta,
+                     torch::Tensor meta_host) {
+  TORCH_CHECK(master.dim() == 1 && w16.dim() == 1 && wt16.dim() == 1 && bhat.dim() == 1 && master.is_contiguous() &&
+                  w16.is_contiguous() && wt16.is_contiguous() && bhat.is_contiguous(),
+              "layerscale_fold: master, w16, wt16 and bhat must be flat contiguous buffers");
+  const float* mp = f32(master, "master");
+  uint16_t* wp = bf_mut(w16, "w16");
+  uint16_t* wtp = bf_mut(wt16, "wt16");
+  float* bp = f32_mut(bhat, "bhat");
+  TORCH_CHECK(w16.device() == master.device() && wt16.device() == master.device() && bhat.device() == master.device() &&
+                  meta.is_cuda() && meta.device() == master.device(),
+              "layerscale_fold: every buffer and meta on the same GPU");
+  TORCH_CHECK(w16.numel() == wt16.numel() && w16.data_ptr() != wt16.data_ptr(), "layerscale_fold: w16 and wt16 are two buffers of one size");
+  for (const void* p : {(const void*)mp, (const void*)wp, (const void*)wtp, (const void*)bp})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(p) % 16 == 0, "layerscale_fold: buffers must be 16-byte aligned");
+  TORCH_CHECK(meta.scalar_type() == torch::kInt64 && meta.dim() == 2 && meta.size(1) == 8 && meta.is_contiguous(),
+              "layerscale_fold: meta must be int64 [n, 8]");
+  TORCH_CHECK(!meta_host.is_cuda() && meta_host.scalar_type() == torch::kInt64 && meta_host.is_contiguous() &&
+                  meta_host.sizes() == meta.sizes(),
+              "layerscale_fold: meta_host must be the host copy of meta (int64 [n, 8])");
+  const int64_t n = meta.size(0);
+  const int64_t* h = meta_host.data_ptr<int64_t>();
+  int64_t tiles = 0;
+  for (int64_t t = 0; t < n; ++t) {
+    const int64_t woff = h[t * 8], goff = h[t * 8 + 1], boff = h[t * 8 + 2], R = h[t * 8 + 3], C = h[t * 8 + 4];
+    const int64_t ooff = h[t * 8 + 5], hoff = h[t * 8 + 6];
+    TORCH_CHECK(R > 0 && C > 0 && R % 8 == 0 && C % 8 == 0 && R < (1 << 24) && C < (1 << 24),
+                "layerscale_fold: R and C must be positive multiples of 8, got ", R, " x ", C);
+    TORCH_CHECK(woff >= 0 && goff >= 0 && boff >= 0 && ooff >= 0 && hoff >= 0 && woff % 8 == 0 && ooff % 8 == 0,
+                "layerscale_fold: offsets must be non-negative, those of W and of its copies multiples of 8");
+    TORCH_CHECK(woff + R * C <= master.numel() && goff + R <= master.numel() && boff + R <= master.numel(),
+                "layerscale_fold: row ", t, " reads outside master");
+    TORCH_CHECK(ooff + R * C <= w16.numel() && hoff + R <= bhat.numel(), "layerscale_fold: row ", t, " writes outside its output");
+    TORCH_CHECK(h[t * 8 + 7] == tiles, "layerscale_fold: row ", t, " tile prefix");
+    tiles += ((R + 63) / 64) * ((C + 63) / 64);
+  }
+  TORCH_CHECK(tiles < (int64_t(1) << 31), "layerscale_fold: too many tiles");
+  check(pvr_layerscale_fold(mp, wp, wtp, bp, meta.data_ptr<int64_t>(), (int)n, (int)tiles, stream()), "layerscale_fold");
+}
+
+// LayerScale unfold (csrc/layerscale.hip): gW / gb / gg (each optional) += the gradients of W [R, C], b [R]
+// and the scale g [R] from dw_hat [R, C] and db_hat [R], the gradients of the folded pair.
+void layerscale_unfold(torch::Tensor dw_hat, torch::Tensor db_hat, torch::Tensor W, torch::Tensor b, torch::Tensor g,
+                       c10::optional<torch::Tensor> gW, c10::optional<torch::Tensor> gb, c10::optional<torch::Tensor> gg) {
+  TORCH_CHECK(W.dim() == 2 && W.is_contiguous(), "layerscale_unfold: W must be a contiguous [R, C] matrix");
+  const int64_t R = W.size(0), C = W.size(1);
+  TORCH_CHECK(R > 0 && C > 0 && R % 8 == 0 && C % 8 == 0 && R < (int64_t(1) << 31) && C < (int64_t(1) << 31),
+              "layerscale_unfold: R and C must be positive multiples of 8, got ", R, " x ", C);
+  bool vec = true;
+  auto mat = [&](const torch::Tensor& t, const char* name) {
+    TORCH_CHECK(t.dim() == 2 && t.size(0) == R && t.size(1) == C && t.is_contiguous() && t.device() == W.device(),
+                "layerscale_unfold: ", name, " must be a contiguous [", R, ", ", C, "] matrix on W's GPU");
+    vec = vec && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+    return f32(t, name);
+  };
+  auto vecr = [&](const torch::Tensor& t, const char* name) {
+    TORCH_CHECK(t.dim() == 1 && t.size(0) == R && t.is_contiguous() && t.device() == W.device(),
+                "layerscale_unfold: ", name, " must be a contiguous [", R, "] vector on W's GPU");
+    return f32(t, name);
+  };
+  const float* wp = mat(W, "W");
+  const float* dwp = mat(dw_hat, "dw_hat");
+  const float* dbp = vecr(db_hat, "db_hat");
+  const float* bp = vecr(b, "b");
+  const float* gp = vecr(g, "g");
+  float* gWp = gW.has_value() && gW->defined() ? const_cast<float*>(mat(*gW, "gW")) : nullptr;
+  float* gbp = gb.has_value() && gb->defined() ? const_cast<float*>(vecr(*gb, "gb")) : nullptr;
+  float* ggp = gg.has_value() && gg->defined() ? const_cast<float*>(vecr(*gg, "gg")) : nullptr;
+  check(pvr_layerscale_unfold(dwp, dbp, wp, bp, gp, gWp, gbp, ggp, (int)R, (int)C, vec ? 1 : 0, stream()), "layerscale_unfold");
+}
+
 void scale_by_clip(torch::Tensor g, torch::Tensor clip) {
   check(pvr_scale_by_clip(f32_mut(g, "g"), g.numel(), f32(clip, "clip"), stream()), "scale_by_clip");
 }
@@ -1715,6 +1789,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("metrics_accum", &metrics_accum);
   m.def("rng_next", &rng_next);
   m.def("zero_f32", &zero_f32);
+  m.def("layerscale_fold", &layerscale_fold, py::arg("master"), py::arg("w16"), py::arg("wt16"), py::arg("bhat"), py::arg("meta"),
+        py::arg("meta_host"));
+  m.def("layerscale_unfold", &layerscale_unfold, py::arg("dw_hat"), py::arg("db_hat"), py::arg("W"), py::arg("b"), py::arg("g"),
+        py::arg("gW") = py::none(), py::arg("gb") = py::none(), py::arg("gg") = py::none());
   m.def("gemm_fp8", &gemm_fp8, py::arg("A"), py::arg("fmt_a"), py::arg("B"), py::arg("fmt_b"), py::arg("C"), py::arg("M"),
         py::arg("N"), py::arg("K"), py::arg("epi"), py::arg("scale_a"), py::arg("scale_b"), py::arg("bias") = py::none(),
         py::arg("resid") = py::none(), py::arg("aux") = py::none(), py::arg("seed") = py::none(), py::arg("seed_offset") = 0,

@@ -287,6 +287,19 @@ hipError_t pvr_xent_soft(const float* logits, int64_t ld, const int64_t* ya, con
 hipError_t pvr_bce(const float* logits, int64_t ld, const int64_t* ya, const int64_t* yb, const float* lam, float eps, float thr,
                    int B, int C, float row_scale, float* loss_rows, float* dlogits, int* correct, float grad_scale, hipStream_t s);
 
+// ---- layerscale.hip
+// LayerScale folded into the last Linear of a residual branch. One launch over every scaled weight: meta
+// int64 [nmat][8] = {W offset, g offset, b offset (in master, fp32), R, C, offset in w16 / wt16, offset in
+// bhat, tile prefix}; R, C and every offset multiples of 8; total_tiles = sum of 64x64 tiles. Writes
+// w16 [R][C] = bf16_rne(fl32(g[i] * W[i][j])), wt16 [C][R] the same values transposed, bhat [R] = fl32(g[i] * b[i]).
+hipError_t pvr_layerscale_fold(const float* master, uint16_t* w16, uint16_t* wt16, float* bhat, const int64_t* meta, int nmat,
+                               int total_tiles, hipStream_t s);
+// The gradients of (W [R][C], b [R], g [R]) from those of the folded pair, dWh [R][C] and dbh [R]:
+// gW += g[i] * dWh, gb += g[i] * dbh, gg[i] += dot(dWh[i], W[i]) + dbh[i] * b[i]; a null destination is
+// skipped. One workgroup per row, no atomics. vec: every pointer is 16-byte aligned and C % 4 == 0.
+hipError_t pvr_layerscale_unfold(const float* dWh, const float* dbh, const float* W, const float* b, const float* g, float* gW,
+                                 float* gb, float* gg, int R, int C, int vec, hipStream_t s);
+
 // ---- optim.hip
 int pvr_norm_partial_blocks();
 // workspace: NORM_BLOCKS floats. out: 3 floats.

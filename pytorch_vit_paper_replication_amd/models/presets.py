@@ -16,10 +16,11 @@ PRESETS: Dict[str, Dict] = {
 
 
 def vit(name: str, image_size: int = 224, num_classes: int = 1000, drop_path: float = 0.0,
-        drop_path_schedule: str = "linear", patch_dropout: float = 0.0, **overrides) -> ViT:
+        drop_path_schedule: str = "linear", patch_dropout: float = 0.0, layer_scale=None, **overrides) -> ViT:
     """``drop_path`` > 0: stochastic depth at that rate (:meth:`ViT.set_drop_path`; the from-scratch recipes
     use 0.1 for ViT-B and more for ViT-L / ViT-H). ``patch_dropout`` > 0: training keeps a random subset of
-    each image's patch tokens (:meth:`ViT.set_patch_dropout`; PatchDropout reports 0.25 - 0.5 at small cost)."""
+    each image's patch tokens (:meth:`ViT.set_patch_dropout`; PatchDropout reports 0.25 - 0.5 at small cost).
+    ``layer_scale`` (a float; None: off): LayerScale initialised to it (:meth:`ViT.set_layer_scale`; DeiT-III uses 1e-4)."""
     cfg = dict(PRESETS[name])
     cfg.update(overrides)
     model = ViT(image_size=image_size, num_classes=num_classes, **cfg)
@@ -27,6 +28,8 @@ def vit(name: str, image_size: int = 224, num_classes: int = 1000, drop_path: fl
         model.set_drop_path(drop_path, drop_path_schedule)
     if patch_dropout:
         model.set_patch_dropout(patch_dropout)
+    if layer_scale is not None:
+        model.set_layer_scale(layer_scale)
     return model
 
 

@@ -215,7 +215,10 @@ class TransformerEncoderBlock(nn.Module):
 
     ``drop_path`` (attribute, default 0; set by :meth:`ViT.set_drop_path`): stochastic depth. In training
     each sample drops each of the two residual branches independently with this probability, and a
-    kept branch is scaled by ``drop_path_keep_scale``: ``x = x + s[b] * branch(x)``."""
+    kept branch is scaled by ``drop_path_keep_scale``: ``x = x + s[b] * branch(x)``.
+
+    ``layer_scale_1`` / ``layer_scale_2`` (parameters ``[D]``, absent by default; registered by
+    :meth:`ViT.set_layer_scale`): LayerScale, ``x = x + s[b] * g1 * MSA(LN(x))``, ``x = x + s[b] * g2 * MLP(LN(x))``."""
 
     def __init__(self, embedding_dim: int = 768, num_heads: int = 12, attn_dropout: float = 0,
                  mlp_size: int = 3072, mlp_dropout: float = 0.1):
@@ -227,6 +230,13 @@ class TransformerEncoderBlock(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         p = self.drop_path if self.training else 0.0
+        g1, g2 = getattr(self, "layer_scale_1", None), getattr(self, "layer_scale_2", None)
+        if g1 is not None:  # LayerScale: each branch times its vector, before the drop-path factor and the residual add
+            if p <= 0.0 or drop_path_thr(p) == 0:
+                x = g1 * self.msa_block(x) + x
+                return g2 * self.mlp_block(x) + x
+            x = self._drop_path_scale(x, p, 0) * (g1 * self.msa_block(x)) + x
+            return self._drop_path_scale(x, p, 1) * (g2 * self.mlp_block(x)) + x
         if p <= 0.0 or drop_path_thr(p) == 0:
             x = self.msa_block(x) + x
             x = self.mlp_block(x) + x
@@ -249,9 +259,20 @@ class TransformerEncoderBlock(nn.Module):
     def fused_params(self):
         m, p = self.msa_block, self.mlp_block
         a = m.multi_head_attention
-        return (m.layer_norm.weight, m.layer_norm.bias, a.in_proj_weight, a.in_proj_bias,
-                a.out_proj.weight, a.out_proj.bias, p.layer_norm.weight, p.layer_norm.bias,
-                p.mlp[0].weight, p.mlp[0].bias, p.mlp[3].weight, p.mlp[3].bias)
+        ps = (m.layer_norm.weight, m.layer_norm.bias, a.in_proj_weight, a.in_proj_bias,
+              a.out_proj.weight, a.out_proj.bias, p.layer_norm.weight, p.layer_norm.bias,
+              p.mlp[0].weight, p.mlp[0].bias, p.mlp[3].weight, p.mlp[3].bias)
+        g1 = getattr(self, "layer_scale_1", None)
+        # LayerScale: the two scales follow the twelve (a block without them passes what it always passed)
+        return ps if g1 is None else ps + (g1, self.layer_scale_2)
+
+    def folded_triples(self):
+        """LayerScale: ``(W, b, g)`` of the two scaled Linear layers, the out-projection with ``layer_scale_1`` and
+        fc2 with ``layer_scale_2`` (empty without the option)."""
+        if getattr(self, "layer_scale_1", None) is None:
+            return []
+        out, fc2 = self.msa_block.multi_head_attention.out_proj, self.mlp_block.mlp[3]
+        return [(out.weight, out.bias, self.layer_scale_1), (fc2.weight, fc2.bias, self.layer_scale_2)]
 
 
 class ViT(nn.Module):
@@ -338,6 +359,57 @@ class ViT(nn.Module):
     def drop_path_rates(self):
         """The per-block rates in effect (all 0 without :meth:`set_drop_path`)."""
         return [float(getattr(blk, "drop_path", 0.0)) for blk in self.transformer_encoder]
+
+    # ------------------------------------------------------------------ LayerScale
+    def set_layer_scale(self, init_values: Optional[float]) -> "ViT":
+        """LayerScale (Touvron et al. 2021, "Going deeper with Image Transformers"; every block of DeiT-III): a
+        learnable per-channel vector on each residual branch, ``x = x + g1 * MSA(LN(x))``, ``x = x + g2 * MLP(LN(x))``.
+        Registers ``layer_scale_1`` and ``layer_scale_2`` (``nn.Parameter [D]`` filled with ``init_values``; DeiT-III
+        uses ``1e-4``) on every encoder block, so ``state_dict()`` grows from 152 to ``152 + 2 L`` keys; ``None``
+        removes them again and the model is what it was. The constructor signature is unchanged; the value is
+        kept in ``config["layer_scale"]``. 1-D parameters: ``param_groups_weight_decay`` does not decay them.
+
+        Call it before the optimizer is built and before the first fused forward (the flat parameter store lays
+        the parameters out once): with a store already covering the model it raises ``RuntimeError``.
+
+        On the fused path the scale is folded into the branch's last Linear (the out-projection, fc2): once per
+        weight change one kernel writes bf16 ``diag(g) W`` (row-major and transposed) and fp32 ``g * b``
+        (``csrc/layerscale.hip``), every forward and dgrad GEMM reads those, and in the backward an unfold kernel
+        turns the gradients of the folded pair into those of ``W``, ``b`` and ``g``. Dropout and drop path are
+        element and row factors and commute with ``g``. Not with :meth:`enable_fp8`.
+        :meth:`folded_state_dict` exports the plain model that computes the same function."""
+        st = getattr(self, "_pvr_store", None)
+        if st is not None and st.covers(self):
+            raise RuntimeError("set_layer_scale() must run before the first fused forward and before the optimizer is "
+                               "built: a ParamStore already covers this model's parameters")
+        for blk in self.transformer_encoder:
+            like = blk.msa_block.layer_norm.weight
+            for name in ("layer_scale_1", "layer_scale_2"):
+                if name in blk._parameters:
+                    del blk._parameters[name]
+                if init_values is not None:
+                    blk.register_parameter(name, nn.Parameter(torch.full_like(like.detach(), float(init_values))))
+        if init_values is None:
+            self.config.pop("layer_scale", None)
+        else:
+            self.config["layer_scale"] = float(init_values)
+        return self
+
+    def has_layer_scale(self) -> bool:
+        return any(getattr(blk, "layer_scale_1", None) is not None for blk in self.transformer_encoder)
+
+    def folded_state_dict(self) -> dict:
+        """The ``state_dict()`` of the plain model (no ``layer_scale_*`` keys: 152 for a classifier) that computes
+        this model's function: each block's out-projection and fc2 hold ``g[:, None] * W`` and ``g * b``, one
+        multiply in the parameters' dtype. The deployment export of a LayerScale model (detached copies);
+        without the option a copy of ``state_dict()``."""
+        sd = {k: v.detach().clone() for k, v in self.state_dict().items() if ".layer_scale_" not in k}
+        for i, blk in enumerate(self.transformer_encoder):
+            names = (f"transformer_encoder.{i}.msa_block.multi_head_attention.out_proj", f"transformer_encoder.{i}.mlp_block.mlp.3")
+            for (w, b, g), name in zip(blk.folded_triples(), names):
+                sd[name + ".weight"] = g.detach()[:, None] * w.detach()
+                sd[name + ".bias"] = g.detach() * b.detach()
+        return sd
 
     # ------------------------------------------------------------------ patch dropout
     def set_patch_dropout(self, rate: float) -> "ViT":
@@ -533,6 +605,11 @@ class ViT(nn.Module):
             raise NotImplementedError(
                 "enable_fp8() does not combine with set_patch_dropout(): the fp8 scaling state is sized by the token "
                 "count, which would differ between training and evaluation; turn one of the two off")
+        layer_scale = self.has_layer_scale()
+        if layer_scale and getattr(self, "_fp8_cfg", None) is not None:
+            raise NotImplementedError(
+                "enable_fp8() does not combine with set_layer_scale(): the fp8 weight copies of the out-projection and "
+                "fc2 would have to be taken from the folded weights; turn one of the two off")
         for p in self.parameters():
             if p.device != dev:
                 raise RuntimeError(f"input is on {dev} but model parameters are on {p.device}")
@@ -543,6 +620,13 @@ class ViT(nn.Module):
             store.register_transposed([w for blk in self.transformer_encoder for w in blk.fused_params()[2:12:2] if w.dim() == 2])
             store._vit_t_registered = True
         store.ensure_transposed()
+        if layer_scale:
+            # LayerScale: the folded copies of the out-projections and fc2 follow the shadows (one launch per
+            # optimizer step or weight exchange, none while ``store.generation`` stands still)
+            if not getattr(store, "_vit_fold_registered", False):
+                store.register_folded([t for blk in self.transformer_encoder for t in blk.folded_triples()])
+                store._vit_fold_registered = True
+            store.fold()
         training = self.training
         grad = torch.is_grad_enabled()
         store.grad_enabled = grad  # the fused Functions' forward runs with grad mode off: tell them

@@ -250,6 +250,34 @@ def _ln_grad_quant(f8d, which: int, shape, device):
     return kw, (q, meta.dscale[slot:slot + 1])
 
 
+def _needs_grad(*params) -> bool:
+    return any(p is not None and p.requires_grad for p in params)
+
+
+def _bias_scratch(R: int, device) -> torch.Tensor:
+    """Zeroed fp32 [R]: the destination of a folded bias's gradient (LayerScale), read by the unfold."""
+    return torch.zeros(R, dtype=torch.float32, device=device)
+
+
+def _scaled_operands(store, ls, w, b):
+    """(bf16 W, bf16 W^T or None, fp32 bias) that the GEMMs of a branch's last Linear read: with LayerScale
+    (``ls`` the branch's scale) the store's folded copies ``diag(g) W`` and ``g * b``, else W's shadows and b."""
+    if ls is None:
+        return store.bf16(w), store.bf16_t(w), b
+    w16, wt16 = store.folded_w(w)
+    return w16, wt16, (store.folded_b(b) if b is not None else None)  # (the dgrads pass no bias)
+
+
+def _scaled_wgrad(wgrad, dy, x, w, b, ls, db_hat, dests):
+    """Weight gradient of a LayerScale branch's last Linear (runs inside the side-stream closure): the GEMM
+    accumulates ``dy^T x`` into a zeroed scratch (allocated here, so the side stream's allocator owns it),
+    which with ``db_hat`` (the folded bias's gradient, a scratch of the main stream that the closure's
+    caller holds) is unfolded into ``dests`` = the gradient views of (W, b, scale), None for a frozen one."""
+    dw_hat = torch.zeros(w.shape, dtype=torch.float32, device=dy.device)
+    wgrad(dy, x, dw_hat)
+    _ext.ext().layerscale_unfold(dw_hat, db_hat, w, b, ls, *dests)
+
+
 class BlockLink:
     """Backward hand-off between consecutive encoder blocks. Block i's final LayerNorm backward
     produces dx for block i-1 and, in the same pass, block i-1's fc2 dropout backward (dz2) and fc2
@@ -257,16 +285,27 @@ class BlockLink:
     column-sum kernel. ``dp2``: block i-1's MLP-branch drop-path site, whose row scale the same pass
     folds into dz2."""
 
-    __slots__ = ("drop2", "b2", "w2", "dz2", "dz2_q", "done", "dp2")
+    __slots__ = ("drop2", "b2", "w2", "dz2", "dz2_q", "done", "dp2", "ls2", "db2")
 
-    def __init__(self, drop2, b2, w2=None, dp2=None):
+    def __init__(self, drop2, b2, w2=None, dp2=None, ls2=None):
         self.drop2, self.b2, self.w2, self.dz2, self.dz2_q, self.done, self.dp2 = drop2, b2, w2, None, None, False, dp2
+        # LayerScale: block i-1's MLP-branch scale (None: none). Its fc2 bias gradient is then that of the folded
+        # bias: the producing pass sums it into the zeroed scratch ``db2``, which block i-1's unfold reads
+        self.ls2, self.db2 = ls2, None
+
+    def bias_dest(self, store, D: int, device):
+        """Where the pass that produces this block's fc2 bias gradient sums it: the gradient view, or with
+        LayerScale a zeroed fp32 scratch [D] kept in ``db2`` (None: nothing needs it)."""
+        if self.ls2 is None:
+            return store.grad_dest(self.b2)
+        self.db2 = _bias_scratch(D, device) if _needs_grad(self.w2, self.b2, self.ls2) else None
+        return self.db2
 
 
 def block_links(blocks, drops2, dps2=None):
     """(own link, previous block's link) per block, for EncoderBlockFn's ``links`` argument."""
     dps2 = dps2 if dps2 is not None else [None] * len(drops2)
-    own = [BlockLink(d, blk.mlp_block.mlp[3].bias, blk.mlp_block.mlp[3].weight, dp)
+    own = [BlockLink(d, blk.mlp_block.mlp[3].bias, blk.mlp_block.mlp[3].weight, dp, getattr(blk, "layer_scale_2", None))
            for blk, d, dp in zip(blocks, drops2, dps2)]
     return [(own[i], own[i - 1] if i else None) for i in range(len(own))]
 
@@ -283,7 +322,11 @@ class EncoderBlockFn(torch.autograd.Function):
             raise NotImplementedError("enable_fp8() does not combine with set_drop_path(): the fp8 gradient copies "
                                       "would have to be taken from the drop-path-scaled gradients")
         aseed, aoff, ap = gemm._drop_args(dropa)
-        ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, w1, b1, w2, b2 = params
+        ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, w1, b1, w2, b2 = params[:12]
+        ls1, ls2 = params[12:] if len(params) > 12 else (None, None)  # LayerScale: the branches' scales
+        if f8 is not None and ls1 is not None:
+            raise NotImplementedError("enable_fp8() does not combine with set_layer_scale(): the fp8 weight copies "
+                                      "would have to be taken from the folded weights")
         T, D = x.shape
         ctx.links = links if links is not None else (None, None)
         # fp8 dgrad GEMMs (e5m2 gradients x e4m3 W^T) only if the model asked for them:
@@ -320,10 +363,12 @@ class EncoderBlockFn(torch.autograd.Function):
         if f8 is None:
             qkv = gemm.linear_fwd(xn1, store.bf16(wqkv), bqkv)
             o, lse = ext.attn_fwd(qkv, B, N, H, scale, aseed, aoff, ap)
-            x1 = gemm.linear_fwd(o, store.bf16(wo), bo, resid=x, drop_path=_dp(dpa, N))
+            wo16, _, bo_r = _scaled_operands(store, ls1, wo, bo)
+            w2_16, _, b2_r = _scaled_operands(store, ls2, w2, b2)
+            x1 = gemm.linear_fwd(o, wo16, bo_r, resid=x, drop_path=_dp(dpa, N))
             xn2, mean2, rstd2 = ext.layernorm_fwd(x1, ln2w, ln2b, eps2, T, D)
             h = gemm.linear_fwd(xn2, store.bf16(w1), b1, gelu_aux=u, gelu=True, drop=drop1)
-            x2 = gemm.linear_fwd(h, store.bf16(w2), b2, resid=x1, drop=drop2, drop_path=_dp(dpm, N))
+            x2 = gemm.linear_fwd(h, w2_16, b2_r, resid=x1, drop=drop2, drop_path=_dp(dpm, N))
         else:
             # fp8 forward GEMMs (e4m3 x e4m3, per-tensor delayed scaling); everything the backward
             # saves stays bf16, so the backward below is unchanged
@@ -387,7 +432,9 @@ class EncoderBlockFn(torch.autograd.Function):
         x, xn1, mean1, rstd1, qkv, o, lse, x1, xn2, mean2, rstd2, u, h = ctx.saved_tensors
         B, N, H, scale, store, drop1, drop2, dropa, params = ctx.meta
         dpa, dpm = ctx.dpath
-        ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, w1, b1, w2, b2 = params
+        ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, w1, b1, w2, b2 = params[:12]
+        ls1, ls2 = params[12:] if len(params) > 12 else (None, None)
+        scaled = {id(wo): ls1, id(w2): ls2}  # LayerScale: these two read the folded copies
         aseed, aoff, ap = gemm._drop_args(dropa)
         g = store.grad_dest
         dx2 = dx2.contiguous()
@@ -410,7 +457,7 @@ class EncoderBlockFn(torch.autograd.Function):
             return tuple(t for t in ts if t is not None)
 
         def dgrad(dy, w, which, dgelu_aux=None, colsum=None, skip_out=False):
-            wt = store.bf16_t(w)
+            w16, wt, _ = _scaled_operands(store, scaled.get(id(w)), w, None)
             if f8d is not None and wt is not None:
                 from . import fp8 as F8
 
@@ -427,7 +474,7 @@ class EncoderBlockFn(torch.autograd.Function):
                     out, pre_q[1] = out
                     _poison(out, skip)
             else:
-                out = gemm.linear_dgrad(dy, store.bf16(w), dgelu_aux=dgelu_aux, wt=wt, colsum=colsum)
+                out = gemm.linear_dgrad(dy, w16, dgelu_aux=dgelu_aux, wt=wt, colsum=colsum)
             if DGRAD_TAP is not None:
                 DGRAD_TAP(which, out)
             return out
@@ -440,12 +487,19 @@ class EncoderBlockFn(torch.autograd.Function):
             else:
                 gemm.linear_wgrad(dy, x, gw)
 
+        # LayerScale: the gradients of a scaled Linear's folded pair go to zeroed scratch (the bias's here, on
+        # this stream; the weight's inside the side-stream closure), and the unfold turns them into those of
+        # W, b and the scale (None: the branch has no scale, or nothing of it trains)
+        gb2 = g(b2) if ls2 is not None else None
+        db2 = None
         # ---- MLP branch: x2 = x1 + drop2(h . W2^T + b2),  h = drop1(gelu(u)),  u = xn2 . W1^T + b1
         if own is not None and own.done:
             # the next block's LayerNorm backward already produced dz2 and d(b2) (and, on the fp8
             # path, dz2's e5m2 copy: no quantize pass before the fc2 dgrad)
             dz2 = own.dz2 if own.dz2 is not None else dx2
             own.dz2 = None
+            if ls2 is not None:
+                db2, own.db2 = own.db2, None
             if own.dz2_q is not None:
                 if f8d is not None:
                     pre_q[0] = own.dz2_q
@@ -454,13 +508,17 @@ class EncoderBlockFn(torch.autograd.Function):
             # last block: the column-sum pass that reduces d(b2) (and applies the fc2 dropout) also
             # writes dz2's e5m2 copy for the fp8 fc2 dgrad once that slot is calibrated
             prod = f8d[0].grad_producer(f8d[1], 0) if f8d is not None and store.bf16_t(w2) is not None else None
+            if ls2 is None:
+                db2 = g(b2)
+            elif _needs_grad(w2, b2, ls2):
+                db2 = _bias_scratch(D, dx2.device)
             if drop2 is not None or dpm is not None:
                 # (drop path: dz2 = s_m * mask2 * dx2, the last block has no next block's LayerNorm backward to ride on)
                 dz2 = torch.empty_like(dx2)
-                r = gemm.bias_grad(dx2, g(b2), drop=drop2, dz=dz2, quant=prod, drop_path=_dp(dpm, N))
+                r = gemm.bias_grad(dx2, db2, drop=drop2, dz=dz2, quant=prod, drop_path=_dp(dpm, N))
             else:
                 dz2 = dx2
-                r = gemm.bias_grad(dx2, g(b2), quant=prod) if (b2.requires_grad or prod is not None) else None
+                r = gemm.bias_grad(dx2, db2, quant=prod) if (db2 is not None or prod is not None) else None
             if prod is not None:
                 pre_q[0] = r
         # dU = (dz2 . W2) * mask*scale*gelu'(u), with d(b1) = colsum(dU) reduced in the same epilogue
@@ -477,13 +535,19 @@ class EncoderBlockFn(torch.autograd.Function):
         if det and gb1 is not None:
             gemm.bias_grad(du, gb1)
 
+        gls2 = g(ls2) if ls2 is not None else None
+
         def mlp_wgrads():
-            if gw2 is not None:
+            if ls2 is not None:
+                if db2 is not None:
+                    _scaled_wgrad(lambda dy, a, out: wgrad(dy, a, out, 0, 3), dz2, h, w2, b2, ls2, db2, (gw2, gb2, gls2))
+            elif gw2 is not None:
                 wgrad(dz2, h, gw2, 0, 3)
             if gw1 is not None:
                 wgrad(du, xn2, gw1, 1, 2)
 
-        store.on_side(mlp_wgrads, dz2, h, du, xn2, *side8(0, 1))  # weight grads off the critical path
+        # weight grads off the critical path
+        store.on_side(mlp_wgrads, dz2, h, du, xn2, *side8(0, 1), *(() if ls2 is None or db2 is None else (db2,)))
         dxn2 = dgrad(du, w1, 1)
         dx1 = torch.empty_like(dx2)
         # dx1 = dx2 + LN2'(dxn2); d(bo) = colsum(dx1) reduced in the same kernel; on the fp8 path the
@@ -492,13 +556,17 @@ class EncoderBlockFn(torch.autograd.Function):
         # drop path: the same pass also writes dz1 = s_a * dx1, the gradient of the attention branch
         # (out-projection dgrad / weight gradient operand), and d(bo) becomes colsum(dz1)
         dz1 = torch.empty_like(dx1) if dpa is not None else dx1
-        ext.layernorm_bwd(dxn2, D, x1, D, mean2, rstd2, ln2w, dx2, D, dx1, D, g(ln2w), g(ln2b), T, dsum=g(bo),
+        gbo = g(bo)
+        dbo = gbo if ls1 is None else (_bias_scratch(D, dx2.device) if _needs_grad(wo, bo, ls1) else None)
+        ext.layernorm_bwd(dxn2, D, x1, D, mean2, rstd2, ln2w, dx2, D, dx1, D, g(ln2w), g(ln2b), T, dsum=dbo,
                           **(dict(dz=dz1, **gemm._drop_path_kw(_dp(dpa, N))) if dpa is not None else {}), **q_kw)
         if q_dx1 is not None:
             pre_q[2] = q_dx1
-        store.grad_ready([w2, b2, w1, b1, ln2w, ln2b])
+        # (without a bucket that ends on the scale's gradient being told of it, that bucket never completes)
+        store.grad_ready([w2, b2, w1, b1, ln2w, ln2b] + ([ls2] if ls2 is not None else []))
         # ---- attention branch: x1 = x + s_a * (attn(qkv(xn1)) . Wo^T + bo)
         gwo, gwqkv = g(wo), g(wqkv)
+        gls1 = g(ls1) if ls1 is not None else None
         do = dgrad(dz1, wo, 2)
         gbqkv = g(bqkv)
         side_db = False
@@ -548,7 +616,10 @@ class EncoderBlockFn(torch.autograd.Function):
                 gemm.bias_grad(do, gbqkv[2 * D:])
             elif side_db:
                 gemm.bias_grad(dqkv, gbqkv)
-            if gwo is not None:
+            if ls1 is not None:
+                if dbo is not None:
+                    _scaled_wgrad(lambda dy, a, out: wgrad(dy, a, out, 2, 1), dz1, o, wo, bo, ls1, dbo, (gwo, gbo, gls1))
+            elif gwo is not None:
                 wgrad(dz1, o, gwo, 2, 1)
             if gwqkv is not None:
                 wgrad(dqkv, xn1, gwqkv, 3, 0)
@@ -566,7 +637,8 @@ class EncoderBlockFn(torch.autograd.Function):
                 side_db = False
             else:
                 pre_q[3] = f8d[0].grad_quant(dqkv, f8d[1], 3)
-        store.on_side(attn_wgrads, dz1, o, dqkv, xn1, do, *(() if db_part is None else (db_part,)), *side8(2, 3))
+        store.on_side(attn_wgrads, dz1, o, dqkv, xn1, do, *(() if db_part is None else (db_part,)), *side8(2, 3),
+                      *(() if ls1 is None or dbo is None else (dbo,)))
         dxn1 = dgrad(dqkv, wqkv, 3)
         dx = torch.empty_like(dx2)
         if prev is not None:
@@ -583,13 +655,14 @@ class EncoderBlockFn(torch.autograd.Function):
                           and prev.w2 is not None and store.bf16_t(prev.w2) is not None
                           and pf8[0].wgrad_ready(pf8[1], 0, 3))
             ext.layernorm_bwd(dxn1, D, x, D, mean1, rstd1, ln1w, dx1, D, dx, D, g(ln1w), g(ln1b), T,
-                              dsum=g(prev.b2), dz=dzp, seed=seed, seed_offset=soff, drop_p=p, dz_nostore=dz_nostore, **dp_kw, **q_kw)
+                              dsum=prev.bias_dest(store, D, dx.device), dz=dzp, seed=seed, seed_offset=soff, drop_p=p,
+                              dz_nostore=dz_nostore, **dp_kw, **q_kw)
             if dzp is not None:
                 _poison(dzp, dz_nostore)
             prev.dz2, prev.dz2_q, prev.done = dzp, q_dz, True
         else:
             ext.layernorm_bwd(dxn1, D, x, D, mean1, rstd1, ln1w, dx1, D, dx, D, g(ln1w), g(ln1b), T)
-        store.grad_ready([bo, wo, bqkv, wqkv, ln1w, ln1b])
+        store.grad_ready([bo, wo, bqkv, wqkv, ln1w, ln1b] + ([ls1] if ls1 is not None else []))
         return (dx,) + (None,) * (9 + len(params))
 
 
@@ -621,7 +694,8 @@ class EncoderBlockClsFn(torch.autograd.Function):
     def forward(ctx, x, B, N, H, eps1, eps2, store, drops, links, *params):
         ext = _ext.ext()
         drop1, drop2, _, dpa, dpm = _split_drops(drops)
-        ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, w1, b1, w2, b2 = params
+        ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, w1, b1, w2, b2 = params[:12]
+        ls1, ls2 = params[12:] if len(params) > 12 else (None, None)  # LayerScale: the branches' scales
         T, D = x.shape
         ctx.links = links if links is not None else (None, None)
         M = w1.shape[0]
@@ -631,11 +705,13 @@ class EncoderBlockClsFn(torch.autograd.Function):
         qkv = gemm.linear_fwd(xn1, store.bf16(wqkv), bqkv)
         o, lse = ext.attn_cls_fwd(qkv, B, N, H, scale)
         xc = x.view(B, N, D)[:, 0]  # the class-token rows, in place (row stride N * D)
-        x1 = gemm.linear_fwd(o, store.bf16(wo), bo, resid=xc, drop_path=_dp(dpa, 1))
+        wo16, _, bo_r = _scaled_operands(store, ls1, wo, bo)
+        w2_16, _, b2_r = _scaled_operands(store, ls2, w2, b2)
+        x1 = gemm.linear_fwd(o, wo16, bo_r, resid=xc, drop_path=_dp(dpa, 1))
         xn2, mean2, rstd2 = ext.layernorm_fwd(x1, ln2w, ln2b, eps2, B, D)
         u = torch.empty(B, M, dtype=torch.bfloat16, device=x.device) if need_bwd else None
         h = gemm.linear_fwd(xn2, store.bf16(w1), b1, gelu_aux=u, gelu=True, drop=drop1, drop_row_mul=N)
-        x2 = gemm.linear_fwd(h, store.bf16(w2), b2, resid=x1, drop=drop2, drop_row_mul=N, drop_path=_dp(dpm, 1))
+        x2 = gemm.linear_fwd(h, w2_16, b2_r, resid=x1, drop=drop2, drop_row_mul=N, drop_path=_dp(dpm, 1))
         if need_bwd:
             ctx.save_for_backward(x, xn1, mean1, rstd1, qkv, o, lse, x1, xn2, mean2, rstd2, u, h)
         ctx.meta = (B, N, H, scale, store, drop2, params)
@@ -649,26 +725,32 @@ class EncoderBlockClsFn(torch.autograd.Function):
         x, xn1, mean1, rstd1, qkv, o, lse, x1, xn2, mean2, rstd2, u, h = ctx.saved_tensors
         B, N, H, scale, store, drop2, params = ctx.meta
         dpa, dpm = ctx.dpath
-        ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, w1, b1, w2, b2 = params
+        ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, w1, b1, w2, b2 = params[:12]
+        ls1, ls2 = params[12:] if len(params) > 12 else (None, None)
+        scaled = {id(wo): ls1, id(w2): ls2}  # LayerScale: see EncoderBlockFn.backward
         g = store.grad_dest
         dx2 = dx2.contiguous()  # [B, D]: the gradient of the class-token rows
         T, D = x.shape
         _, prev = ctx.links
 
         def dgrad(dy, w, which, dgelu_aux=None, colsum=None):
-            out = gemm.linear_dgrad(dy, store.bf16(w), dgelu_aux=dgelu_aux, wt=store.bf16_t(w), colsum=colsum)
+            w16, wt, _ = _scaled_operands(store, scaled.get(id(w)), w, None)
+            out = gemm.linear_dgrad(dy, w16, dgelu_aux=dgelu_aux, wt=wt, colsum=colsum)
             if DGRAD_TAP is not None:
                 DGRAD_TAP(which, out)
             return out
 
         # ---- MLP branch on B rows (see EncoderBlockFn.backward)
+        gb2 = g(b2)
+        db2 = gb2 if ls2 is None else (_bias_scratch(D, dx2.device) if _needs_grad(w2, b2, ls2) else None)
         if drop2 is not None or dpm is not None:
             dz2 = torch.empty_like(dx2)
-            gemm.bias_grad(dx2, g(b2), drop=drop2, dz=dz2, row_mul=N, drop_path=_dp(dpm, 1))
+            gemm.bias_grad(dx2, db2, drop=drop2, dz=dz2, row_mul=N, drop_path=_dp(dpm, 1))
         else:
             dz2 = dx2
-            if b2.requires_grad:
-                gemm.bias_grad(dx2, g(b2))
+            if db2 is not None:
+                gemm.bias_grad(dx2, db2)
+        gls2 = g(ls2) if ls2 is not None else None
         gb1 = g(b1)
         gw2, gw1 = g(w2), g(w1)
         du = dgrad(dz2, w2, 0, dgelu_aux=u, colsum=None if det else gb1)
@@ -676,32 +758,41 @@ class EncoderBlockClsFn(torch.autograd.Function):
             gemm.bias_grad(du, gb1)
 
         def mlp_wgrads():  # reductions over B tokens
-            if gw2 is not None:
+            if ls2 is not None:
+                if db2 is not None:
+                    _scaled_wgrad(gemm.linear_wgrad, dz2, h, w2, b2, ls2, db2, (gw2, gb2, gls2))
+            elif gw2 is not None:
                 gemm.linear_wgrad(dz2, h, gw2)
             if gw1 is not None:
                 gemm.linear_wgrad(du, xn2, gw1)
 
-        store.on_side(mlp_wgrads, dz2, h, du, xn2)
+        store.on_side(mlp_wgrads, dz2, h, du, xn2, *(() if ls2 is None or db2 is None else (db2,)))
         dxn2 = dgrad(du, w1, 1)
         dx1 = torch.empty_like(dx2)
         dz1 = torch.empty_like(dx1) if dpa is not None else dx1  # drop path: s_a * dx1 (see EncoderBlockFn.backward)
-        ext.layernorm_bwd(dxn2, D, x1, D, mean2, rstd2, ln2w, dx2, D, dx1, D, g(ln2w), g(ln2b), B, dsum=g(bo),
+        gbo = g(bo)
+        dbo = gbo if ls1 is None else (_bias_scratch(D, dx2.device) if _needs_grad(wo, bo, ls1) else None)
+        ext.layernorm_bwd(dxn2, D, x1, D, mean2, rstd2, ln2w, dx2, D, dx1, D, g(ln2w), g(ln2b), B, dsum=dbo,
                           **(dict(dz=dz1, **gemm._drop_path_kw(_dp(dpa, 1))) if dpa is not None else {}))
-        store.grad_ready([w2, b2, w1, b1, ln2w, ln2b])
+        store.grad_ready([w2, b2, w1, b1, ln2w, ln2b] + ([ls2] if ls2 is not None else []))
         # ---- attention branch: the class-token query against every token's K and V
         gwo, gwqkv, gbqkv = g(wo), g(wqkv), g(bqkv)
+        gls1 = g(ls1) if ls1 is not None else None
         do = dgrad(dz1, wo, 2)
         dqkv, dq0 = ext.attn_cls_bwd(do, qkv, o, lse, B, N, H, scale)
 
         def attn_wgrads():
             if gbqkv is not None:
                 ext.attn_cls_dbias(dq0, do, gbqkv.view(-1))
-            if gwo is not None:
+            if ls1 is not None:
+                if dbo is not None:
+                    _scaled_wgrad(gemm.linear_wgrad, dz1, o, wo, bo, ls1, dbo, (gwo, gbo, gls1))
+            elif gwo is not None:
                 gemm.linear_wgrad(dz1, o, gwo)
             if gwqkv is not None:
                 gemm.linear_wgrad(dqkv, xn1, gwqkv)
 
-        store.on_side(attn_wgrads, dz1, o, dqkv, xn1, do, dq0)
+        store.on_side(attn_wgrads, dz1, o, dqkv, xn1, do, dq0, *(() if ls1 is None or dbo is None else (dbo,)))
         dxn1 = dgrad(dqkv, wqkv, 3)
         dx = torch.empty_like(x)
         # dx = LN1'(dxn1) on every row + dx1 on the class-token rows (compact: no zero-filled carrier)
@@ -711,11 +802,12 @@ class EncoderBlockClsFn(torch.autograd.Function):
             dp_kw = gemm._drop_path_kw(_dp(prev.dp2, N))  # every token row of the previous block: N rows per sample
             dzp = torch.empty_like(x) if seed is not None or dp_kw else None
             ext.layernorm_bwd(dxn1, D, x, D, mean1, rstd1, ln1w, dx1, D, dx, D, g(ln1w), g(ln1b), T,
-                              dsum=g(prev.b2), dz=dzp, seed=seed, seed_offset=soff, drop_p=p, dres_every=N, **dp_kw)
+                              dsum=prev.bias_dest(store, D, dx.device), dz=dzp, seed=seed, seed_offset=soff, drop_p=p,
+                              dres_every=N, **dp_kw)
             prev.dz2, prev.dz2_q, prev.done = dzp, None, True
         else:
             ext.layernorm_bwd(dxn1, D, x, D, mean1, rstd1, ln1w, dx1, D, dx, D, g(ln1w), g(ln1b), T, dres_every=N)
-        store.grad_ready([bo, wo, bqkv, wqkv, ln1w, ln1b])
+        store.grad_ready([bo, wo, bqkv, wqkv, ln1w, ln1b] + ([ls1] if ls1 is not None else []))
         return (dx,) + (None,) * (8 + len(params))
 
 

@@ -208,6 +208,60 @@ class ParamStore:
                     self._t_views[id(p)].copy_(self.bf16(p).t())
         self._t_dirty = False
 
+    # ------------------------------------------------------------------ LayerScale: folded copies
+    def register_folded(self, triples) -> None:
+        """Keep folded bf16 copies of these ``(W [R, C], b [R], g [R])`` triples (LayerScale, csrc/layerscale.hip):
+        ``diag(g) W`` row-major and transposed, and ``g * b`` in fp32. The GEMMs of a scaled Linear read them in
+        place of W's shadows and b; :meth:`fold` rebuilds them whenever the shadows changed."""
+        triples = [tuple(t) for t in triples]
+        meta, off, boff, tiles = [], 0, 0, 0
+        for w, b, g in triples:
+            R, C = w.shape
+            if R % 8 or C % 8 or tuple(b.shape) != (R,) or tuple(g.shape) != (R,):
+                raise ValueError(f"register_folded: W [R, C] with R and C multiples of 8, b [R] and g [R], got {tuple(w.shape)}, "
+                                 f"{tuple(b.shape)}, {tuple(g.shape)}")
+            meta.append([self.offset(w), self.offset(g), self.offset(b), R, C, off, boff, tiles])
+            tiles += ((R + 63) // 64) * ((C + 63) // 64)
+            off += (w.numel() + ALIGN - 1) // ALIGN * ALIGN
+            boff += (R + ALIGN - 1) // ALIGN * ALIGN
+        with torch.inference_mode(False), torch.no_grad():
+            self._f_w = torch.empty(max(off, ALIGN), dtype=torch.bfloat16, device=self.device)
+            self._f_wt = torch.empty(max(off, ALIGN), dtype=torch.bfloat16, device=self.device)
+            self._f_b = torch.empty(max(boff, ALIGN), dtype=torch.float32, device=self.device)
+            self._f_meta_host = torch.tensor(meta, dtype=torch.int64).reshape(-1, 8)
+            self._f_meta = self._f_meta_host.to(self.device)
+        self._f_views = {}
+        for (w, b, g), row in zip(triples, meta):
+            R, C, o, bo = row[3], row[4], row[5], row[6]
+            self._f_views[id(w)] = (self._f_w[o:o + R * C].view(R, C), self._f_wt[o:o + R * C].view(C, R))
+            self._f_views[id(b)] = self._f_b[bo:bo + R]
+        self._f_triples = triples
+        self._f_generation = -1
+
+    def fold(self) -> None:
+        """Rebuild the folded copies if the master changed since the last fold (``generation``): one launch per
+        optimizer step or weight exchange, none between evaluation forwards. Call after ``refresh_shadow``."""
+        if not getattr(self, "_f_triples", None) or self._f_generation == self.generation:
+            return
+        with torch.inference_mode(False), torch.no_grad():
+            if self.flat.is_cuda and _ext.available():
+                _ext.ext().layerscale_fold(self.flat, self._f_w, self._f_wt, self._f_b, self._f_meta, self._f_meta_host)
+            else:
+                for w, b, g in self._f_triples:
+                    w16, wt16 = self._f_views[id(w)]
+                    w16.copy_(g.detach()[:, None] * w.detach())
+                    wt16.copy_(w16.t())
+                    self._f_views[id(b)].copy_(g.detach() * b.detach())
+        self._f_generation = self.generation
+
+    def folded_w(self, w: torch.nn.Parameter):
+        """(bf16 ``diag(g) W`` [R, C], its transpose [C, R]) of a registered weight."""
+        return self._f_views[id(w)]
+
+    def folded_b(self, b: torch.nn.Parameter) -> torch.Tensor:
+        """fp32 ``g * b`` of a registered bias."""
+        return self._f_views[id(b)]
+
     # ------------------------------------------------------------------ another set of weights
     @contextlib.contextmanager
     def swapped(self, flat_other: torch.Tensor):

@@ -92,7 +92,7 @@ def save_checkpoint(target_dir: str, model: torch.nn.Module, optimizer=None, lr_
         state["runtime"] = rt()
     cfg = getattr(_unwrap(model), "config", None)
     if isinstance(cfg, dict):
-        # the constructor arguments and the options set by method (``set_drop_path``, ``set_patch_dropout``): numbers and strings
+        # the constructor arguments and the options set by method (``set_drop_path``, ``set_patch_dropout``, ``set_layer_scale``): numbers and strings
         state["config"] = dict(cfg)
     if model_ema is not None:
         # tensors and numbers only: load_checkpoint reads with weights_only=True
@@ -111,7 +111,8 @@ def load_checkpoint(path: str, model: torch.nn.Module, optimizer=None, lr_schedu
     ``config`` is the saved model's ``config`` dict (None for a model without one, or an older file). It is
     returned, not applied: options that live there and not in ``state_dict()`` (``set_drop_path``,
     ``set_patch_dropout``) are the caller's to set again, e.g. ``model.set_drop_path(cfg["drop_path"],
-    cfg["drop_path_schedule"])`` or ``model.set_patch_dropout(cfg["patch_dropout"])``.
+    cfg["drop_path_schedule"])`` or ``model.set_patch_dropout(cfg["patch_dropout"])``. ``config["layer_scale"]``
+    (``set_layer_scale``) adds parameters, so the caller sets it before this call for the keys to match.
 
     The file is read with ``weights_only=True``: everything ``save_checkpoint`` writes (tensors,
     dicts/lists of numbers, the optimizer and LR-scheduler state dicts, RNG byte tensors) loads
