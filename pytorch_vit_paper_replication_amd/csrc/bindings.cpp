@@ -871,13 +871,17 @@ void patch_bwd(torch::Tensor dE, int64_t B, int64_t ntok, int64_t D, c10::option
 // receives the batch mean of the row losses (a second, one-workgroup launch).
 torch::Tensor xent(torch::Tensor logits, torch::Tensor labels, c10::optional<torch::Tensor> dlogits, c10::optional<torch::Tensor> correct,
                    double grad_scale, c10::optional<torch::Tensor> mean) {
-  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "xent: logits must be [B, C] row-major");
-  TORCH_CHECK(labels.scalar_type() == torch::kInt64 && labels.is_contiguous(), "xent: labels must be contiguous int64");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.size(1) >= 1, "xent: logits must be [B, C] row-major");
   const int64_t B = logits.size(0), C = logits.size(1);
+  // the kernel reads labels[b] for every row b: a short label tensor would be read out of bounds
+  TORCH_CHECK(labels.is_cuda() && labels.device() == logits.device() && labels.scalar_type() == torch::kInt64 && labels.is_contiguous() &&
+                  labels.numel() == B,
+              "xent: labels must be contiguous int64 [B] on the logits' device");
   if (correct.has_value() && correct->defined())
     TORCH_CHECK(correct->is_cuda() && correct->numel() >= B && correct->scalar_type() == torch::kInt32, "xent: correct int32 [B]");
   if (dlogits.has_value() && dlogits->defined())
-    TORCH_CHECK(dlogits->is_contiguous() && dlogits->numel() == B * C && dlogits->scalar_type() == torch::kFloat32, "xent: dlogits f32 [B][C]");
+    TORCH_CHECK(dlogits->is_cuda() && dlogits->is_contiguous() && dlogits->numel() == B * C && dlogits->scalar_type() == torch::kFloat32,
+                "xent: dlogits f32 [B][C]");
   if (mean.has_value() && mean->defined()) TORCH_CHECK(mean->numel() >= 1, "xent: mean [1]");
   auto loss = torch::empty({B}, logits.options().dtype(torch::kFloat32));
   check(pvr_xent(f32(logits, "logits"), logits.stride(0), labels.data_ptr<int64_t>(), (int)B, (int)C, loss.data_ptr<float>(),

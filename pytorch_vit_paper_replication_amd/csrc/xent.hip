@@ -106,7 +106,10 @@ __global__ void __launch_bounds__(256) xent_soft_kernel(const float* __restrict_
   const bool valid = ya >= 0 && ya < C && yb >= 0 && yb < C;  // as xent_kernel: such rows contribute nothing
   const float lam = lam_[b], oml = 1.0f - lam, ome = 1.0f - eps, eoc = eps / (float)C;
   if (tid == 0) {
-    loss_rows[b] = valid ? lse - ome * (lam * x[ya] + oml * x[yb]) - eoc * t : 0.f;
+    // without smoothing the logit sum carries no weight: not 0 * t, which is NaN on a row with a
+    // masked (-inf) class, where t = -inf
+    const float smooth = eoc != 0.f ? eoc * t : 0.f;
+    loss_rows[b] = valid ? lse - ome * (lam * x[ya] + oml * x[yb]) - smooth : 0.f;
     if (correct) correct[b] = mi == (int)ya ? 1 : 0;  // the sample's own label
   }
   if (dlogits) {

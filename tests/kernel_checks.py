@@ -2187,7 +2187,7 @@ def all_checks() -> List[Callable[[], Result]]:
         lambda: check_wgrad_fp8_mn(300, 768, 256),
         lambda: check_fp8_transpose(257, 768, 0),
         lambda: check_layernorm_fwd_q8(50, 768),
-        check_layernorm_bwd_q8,                                   # D 1280 (H/14): 8-column chunks
+        check_layernorm_bwd_q8,                                   # D 1280 (H/14): five 4-column chunks per lane, (MAXCH, W) = (5, 4)
         check_colsum_q8,
         lambda: check_colsum_q8(1001, 2304),
         lambda: check_layernorm_bwd_q8(2000, 768, linked=True),   # D 768: 4-column chunks + dz

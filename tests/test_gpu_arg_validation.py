@@ -228,6 +228,37 @@ def test_cast_f32_bf16_rejects_what_its_kernel_cannot_take(case):
     _passes(KC.check_cast_f32_bf16(5))
 
 
+XENT_BAD = {
+    "labels on the host": lambda a: a.update(labels=a["labels"].cpu()),
+    "labels shorter than the batch": lambda a: a.update(labels=a["labels"][:-1]),
+    "labels longer than the batch": lambda a: a.update(labels=torch.cat([a["labels"], a["labels"]])),
+    "labels int32": lambda a: a.update(labels=a["labels"].int()),
+    "labels strided": lambda a: a.update(labels=_strided(a["labels"])),
+    "logits with no class": lambda a: a.update(logits=a["logits"][:, :0], dlogits=a["dlogits"][:, :0].contiguous()),
+    "dlogits on the host": lambda a: a.update(dlogits=torch.full((4, 7), KC.SENTINEL)),
+}
+
+
+@pytest.mark.parametrize("case", list(XENT_BAD), ids=[c.replace(" ", "_") for c in XENT_BAD])
+def test_xent_rejects_what_its_kernel_cannot_take(case):
+    """``xent`` reads labels[b] for every logits row and writes dlogits through a raw pointer: labels
+    of another length or device, logits without a class and a host dlogits are refused before any
+    launch, as ``xent_soft`` refuses them."""
+    ext = _ext()
+    B, C = 4, 7
+    a = dict(logits=torch.zeros(B, C, device=DEV), labels=torch.arange(B, dtype=torch.int64, device=DEV),
+             dlogits=torch.full((B, C), KC.SENTINEL, device=DEV))
+    dl, corr, mean = a["dlogits"], torch.full((B,), 7, dtype=torch.int32, device=DEV), torch.full((1,), KC.SENTINEL, device=DEV)
+    XENT_BAD[case](a)
+    with pytest.raises(RuntimeError, match="xent: .*(labels must be contiguous int64|logits must be|dlogits f32)"):
+        ext.xent(a["logits"], a["labels"], a["dlogits"], corr, 1.0 / B, mean)
+    torch.cuda.synchronize()
+    assert bool((dl == KC.SENTINEL).all().item()) and bool((corr == 7).all().item()) and bool((mean == KC.SENTINEL).all().item()), \
+        "a rejected call must not launch"
+    torch.manual_seed(7)
+    _passes(KC.check_xent(B, C))
+
+
 def test_cls_rows_needs_its_seed():
     """The CLS rows of the token matrix, rows b * ntok of [B * ntok, D]: dropout(cls + pos[0]).
 
