@@ -36,9 +36,18 @@ def build_parser():
     p.add_argument("--batch-size", type=int, default=32)
     p.add_argument("--lr", type=float, default=1e-3, help="learning rate (LAMB recipes use about 3e-3)")
     p.add_argument("--weight-decay", type=float, default=0.03, help="weight decay (LAMB recipes use 0.02-0.05)")
-    p.add_argument("--optimizer", choices=["adam", "adamw", "lamb"], default="adam",
+    p.add_argument("--optimizer", choices=["adam", "adamw", "lamb", "sgd"], default="adam",
                    help="adam: coupled L2 decay (the reference recipe); adamw: decoupled decay; lamb: Adam's update scaled "
-                        "per parameter tensor by ||w|| / ||update|| (large batches; FusedLamb only)")
+                        "per parameter tensor by ||w|| / ||update|| (large batches; FusedLamb only); sgd: SGD with "
+                        "--momentum (the paper's fine-tuning optimizer, with --weight-decay 0 and --lr-schedule cosine)")
+    p.add_argument("--momentum", type=float, default=0.9, help="with --optimizer sgd: the momentum")
+    p.add_argument("--nesterov", action="store_true", help="with --optimizer sgd: Nesterov momentum")
+    p.add_argument("--lr-schedule", choices=["linear", "cosine"], default="linear",
+                   help="decay after the warmup: linear to 0 (the reference recipe) or cosine")
+    p.add_argument("--init-from", default=None, metavar="PATH",
+                   help="ViT: start from the model weights of this file (a saved model, or a checkpoint's model), nothing "
+                        "else; weights trained at another --image-size get their position embedding resampled, and a "
+                        "classifier of another class count is left freshly initialised")
     p.add_argument("--warmup-frac", type=float, default=0.05)
     p.add_argument("--max-grad-norm", type=float, default=1.0)
     p.add_argument("--num-workers", type=int, default=4)
@@ -49,7 +58,7 @@ def build_parser():
     p.add_argument("--resume", default=None)
     p.add_argument("--metrics", default=None, help="append per-epoch JSONL metrics here")
     p.add_argument("--torch-optimizer", action="store_true",
-                   help="use torch.optim.Adam / AdamW instead of FusedAdam (there is no torch LAMB)")
+                   help="use torch.optim.Adam / AdamW / SGD instead of FusedAdam / FusedSGD (there is no torch LAMB)")
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--dtype", choices=["bf16", "fp8"], default="bf16",
                    help="fp8: the encoder GEMMs in fp8 with delayed scaling (ViT.enable_fp8; GPU fused path only)")
@@ -181,11 +190,47 @@ def build_model(args, ncls: int, rank: int = 0):
     return model
 
 
+def build_optimizer(args, model):
+    """The optimizer of ``--optimizer`` / ``--torch-optimizer`` over the two weight-decay groups of the recipe."""
+    from ..optim import FusedAdam, FusedLamb, FusedSGD, param_groups_weight_decay
+
+    groups = param_groups_weight_decay(model, args.weight_decay)
+    if args.optimizer == "lamb":
+        return FusedLamb(groups, lr=args.lr, betas=(0.9, 0.999))
+    if args.optimizer == "sgd":
+        cls = torch.optim.SGD if args.torch_optimizer else FusedSGD
+        return cls(groups, lr=args.lr, momentum=args.momentum, nesterov=args.nesterov)
+    if args.torch_optimizer:
+        return (torch.optim.AdamW if args.optimizer == "adamw" else torch.optim.Adam)(groups, lr=args.lr, betas=(0.9, 0.999))
+    if args.optimizer == "adamw":
+        return FusedAdam(groups, lr=args.lr, betas=(0.9, 0.999), decoupled_weight_decay=True)
+    return FusedAdam(groups, lr=args.lr, betas=(0.9, 0.999))
+
+
+def init_model_from(model, path: str) -> None:
+    """``--init-from``: the model weights of ``path`` (a saved model's state dict, or the ``"model"`` entry of a
+    checkpoint) into ``model`` through :func:`~..models.transfer.load_state_dict_resized`. A classifier of another
+    shape than the model's is left out, so the model keeps its fresh head; every other key must match."""
+    from ..models.transfer import load_state_dict_resized
+
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    if isinstance(sd.get("model"), dict):
+        sd = sd["model"]
+    own = model.state_dict()
+    fresh = [k for k in sd if k.startswith("classifier.") and k in own and sd[k].shape != own[k].shape]
+    sd = {k: v for k, v in sd.items() if k not in fresh}
+    missing, unexpected = load_state_dict_resized(model, sd, strict=False)
+    if set(missing) - set(fresh) or unexpected:
+        raise SystemExit(f"--init-from {path}: missing keys {sorted(set(missing) - set(fresh))}, unexpected keys {list(unexpected)}")
+    if _is_rank0():
+        print(f"[INFO] Initialised the model from {path}" + (f" (fresh classifier: {', '.join(fresh)})" if fresh else ""))
+
+
 def main(argv=None) -> int:
     from .. import engine
     from ..data import create_dataloaders, create_synthetic_dataloaders
     from ..data.transforms import default_vit_transform, uint8_transform
-    from ..optim import FusedAdam, FusedLamb, ModelEma, param_groups_weight_decay, warmup_linear_decay
+    from ..optim import ModelEma, warmup_cosine_decay, warmup_linear_decay
     from ..parallel import DistributedDataParallel, init_distributed, is_dist
     from .. import _ext
     from ..utils import load_checkpoint, save_model, set_seeds
@@ -214,6 +259,10 @@ def main(argv=None) -> int:
         raise SystemExit("--random-erasing must be in [0, 1]")
     if args.optimizer == "lamb" and args.torch_optimizer:
         raise SystemExit("--optimizer lamb has no torch.optim counterpart: drop --torch-optimizer")
+    if args.nesterov and args.optimizer != "sgd":
+        raise SystemExit("--nesterov needs --optimizer sgd")
+    if args.init_from and args.model == "tinyvgg":
+        raise SystemExit("--init-from applies to the ViT models")
     if args.model_ema_warmup and args.model_ema is None:
         raise SystemExit("--model-ema-warmup needs --model-ema")
     if not args.device_preprocess and (args.augment != "none" or args.source_size is not None):
@@ -244,17 +293,12 @@ def main(argv=None) -> int:
                                                             num_workers=args.num_workers)
     ncls = args.num_classes or len(class_names)
     model = build_model(args, ncls, rank)
+    if args.init_from:
+        init_model_from(model, args.init_from)
     model.to(device)
-    groups = param_groups_weight_decay(model, args.weight_decay)
-    if args.optimizer == "lamb":
-        opt = FusedLamb(groups, lr=args.lr, betas=(0.9, 0.999))
-    elif args.torch_optimizer:
-        opt = (torch.optim.AdamW if args.optimizer == "adamw" else torch.optim.Adam)(groups, lr=args.lr, betas=(0.9, 0.999))
-    elif args.optimizer == "adamw":
-        opt = FusedAdam(groups, lr=args.lr, betas=(0.9, 0.999), decoupled_weight_decay=True)
-    else:
-        opt = FusedAdam(groups, lr=args.lr, betas=(0.9, 0.999))
-    sched = warmup_linear_decay(opt, args.epochs * len(train_dl), args.warmup_frac)
+    opt = build_optimizer(args, model)
+    sched = (warmup_cosine_decay if args.lr_schedule == "cosine" else warmup_linear_decay)(
+        opt, args.epochs * len(train_dl), args.warmup_frac)
     ema = ModelEma(model, decay=args.model_ema, warmup=args.model_ema_warmup) if args.model_ema is not None else None
     start_epoch, results = 0, None
     if args.resume:

@@ -1137,6 +1137,150 @@ void lamb_update(torch::Tensor p, torch::Tensor m, torch::Tensor v, c10::optiona
         who);
 }
 
+// SGD (sgd.hip). Its kernels index the flat buffers through the tables, so the tables' contents are checked
+// too: once, on the host, when they are built. sgd_segments / sgd_tiles take the tables as CPU tensors,
+// check every row against the element counts of the buffers the step will pass, and return an SgdTables
+// holding the device copies; sgd / sgd_t take nothing else as tables, so no unchecked row reaches a kernel
+// and a step needs no device-to-host copy.
+struct SgdTables {
+  bool tiles = false;
+  torch::Tensor seg_start, seg_group;  // the segment-table form
+  torch::Tensor tmeta, fmeta;          // the tile form
+  int64_t ntiles = 0, flat4 = 0;
+  int64_t n = 0, nt = 0;  // elements of p (g, buf, shadow) and of shadow_t the rows were checked against
+  int64_t max_group = -1;  // largest param group a row names
+};
+
+void sgd_host_table(const torch::Tensor& t, torch::ScalarType dt, int64_t cols, const char* who, const char* name) {
+  TORCH_CHECK(!t.is_cuda() && t.scalar_type() == dt && t.is_contiguous() && t.numel() >= 1 && t.numel() < (int64_t(1) << 31) &&
+                  (cols == 0 ? t.dim() == 1 : (t.dim() == 2 && t.size(1) == cols)),
+              who, ": ", name, " must be a contiguous ", (dt == torch::kInt64 ? "int64" : "int32"), " CPU ",
+              cols == 0 ? "vector" : "table", " of >= 1 rows", cols == 0 ? "" : " with ", cols == 0 ? "" : std::to_string(cols),
+              cols == 0 ? "" : " columns");
+}
+
+// seg_start int64 [nseg] (sorted, multiples of 4, first 0, inside [0, n)), seg_group int32 [nseg] (-1 frozen)
+SgdTables sgd_segments(torch::Tensor seg_start, torch::Tensor seg_group, int64_t n, torch::Device device) {
+  const char* who = "sgd_segments";
+  sgd_host_table(seg_start, torch::kInt64, 0, who, "seg_start");
+  sgd_host_table(seg_group, torch::kInt32, 0, who, "seg_group");
+  TORCH_CHECK(seg_start.numel() == seg_group.numel(), who, ": seg_start / seg_group must hold the same number of segments, got ",
+              seg_start.numel(), " and ", seg_group.numel());
+  TORCH_CHECK(n >= 4 && n % 4 == 0, who, ": the flat buffers hold a multiple of 4 elements (the kernel works in float4), got ", n);
+  TORCH_CHECK(device.is_cuda(), who, ": device must be a GPU");
+  SgdTables t;
+  const int64_t* ss = seg_start.data_ptr<int64_t>();
+  const int* sg = seg_group.data_ptr<int>();
+  for (int64_t i = 0; i < seg_start.numel(); ++i) {
+    TORCH_CHECK(ss[i] % 4 == 0, who, ": segment ", i, " starts at element ", ss[i], ", not a multiple of 4 (the kernel works in float4)");
+    TORCH_CHECK(i == 0 ? ss[i] == 0 : ss[i] > ss[i - 1], who, ": seg_start must begin at 0 and rise strictly (segment ", i, ")");
+    TORCH_CHECK(ss[i] < n, who, ": segment ", i, " starts at element ", ss[i], " of ", n);
+    TORCH_CHECK(sg[i] >= -1, who, ": segment ", i, " names group ", sg[i]);
+    t.max_group = std::max<int64_t>(t.max_group, sg[i]);
+  }
+  t.n = n;
+  t.seg_start = seg_start.to(device);
+  t.seg_group = seg_group.to(device);
+  return t;
+}
+
+// tmeta int64 [nmat][6] {flat offset, shadow_t offset, R, C, first tile, group} (R, C % 64 == 0),
+// fmeta int64 [nflat][4] {flat start, elements % 4 == 0, group, first float4}: adam_t's tables.
+// n / nt: elements of the flat buffers and of shadow_t.
+SgdTables sgd_tiles(torch::Tensor tmeta, torch::Tensor fmeta, int64_t n, int64_t nt, torch::Device device) {
+  const char* who = "sgd_tiles";
+  sgd_host_table(tmeta, torch::kInt64, 6, who, "tmeta");
+  sgd_host_table(fmeta, torch::kInt64, 4, who, "fmeta");
+  TORCH_CHECK(n >= 4 && n % 4 == 0 && nt >= 0, who, ": the flat buffers hold a multiple of 4 elements, got ", n);
+  TORCH_CHECK(device.is_cuda(), who, ": device must be a GPU");
+  SgdTables t;
+  t.tiles = true;
+  const int64_t* tm = tmeta.data_ptr<int64_t>();
+  for (int64_t i = 0; i < tmeta.size(0); ++i, tm += 6) {
+    const int64_t soff = tm[0], doff = tm[1], R = tm[2], C = tm[3];
+    TORCH_CHECK(R >= 64 && C >= 64 && R % 64 == 0 && C % 64 == 0 && R < (int64_t(1) << 24) && C < (int64_t(1) << 24), who, ": matrix ",
+                i, " is ", R, " x ", C, ", not multiples of 64");
+    TORCH_CHECK(soff >= 0 && soff % 4 == 0 && soff + R * C <= n, who, ": matrix ", i, " at element ", soff,
+                " must start at a multiple of 4 and lie inside the ", n, " elements of the buffers");
+    TORCH_CHECK(doff >= 0 && doff % 8 == 0 && doff + R * C <= nt, who, ": W^T of matrix ", i, " at element ", doff,
+                " must start at a multiple of 8 and lie inside the ", nt, " elements of shadow_t");
+    TORCH_CHECK(tm[4] == t.ntiles, who, ": matrix ", i, " must name its first tile, ", t.ntiles, ", got ", tm[4]);
+    TORCH_CHECK(tm[5] >= -1 && tm[5] < (int64_t(1) << 31), who, ": matrix ", i, " names group ", tm[5]);
+    t.ntiles += (R / 64) * (C / 64);
+    t.max_group = std::max(t.max_group, tm[5]);
+  }
+  TORCH_CHECK(t.ntiles < (int64_t(1) << 31), who, ": too many tiles");
+  const int64_t* fm = fmeta.data_ptr<int64_t>();
+  for (int64_t i = 0; i < fmeta.size(0); ++i, fm += 4) {
+    TORCH_CHECK(fm[0] >= 0 && fm[0] % 4 == 0 && fm[1] >= 4 && fm[1] % 4 == 0 && fm[1] <= n && fm[0] <= n - fm[1], who, ": range ", i,
+                " (start ", fm[0], ", ", fm[1], " elements) must start at and hold a multiple of 4 inside the ", n,
+                " elements of the buffers");
+    TORCH_CHECK(fm[3] == t.flat4, who, ": range ", i, " must name its first float4, ", t.flat4, ", got ", fm[3]);
+    TORCH_CHECK(fm[2] >= -1 && fm[2] < (int64_t(1) << 31), who, ": range ", i, " names group ", fm[2]);
+    t.flat4 += fm[1] / 4;
+    t.max_group = std::max(t.max_group, fm[2]);
+  }
+  t.n = n;
+  t.nt = nt;
+  t.tmeta = tmeta.to(device);
+  t.fmeta = fmeta.to(device);
+  return t;
+}
+
+// What sgd and sgd_t share: the buffers against the element count the tables were checked for
+const GroupTable sgd_common(const SgdTables& t, const torch::Tensor& p, const torch::Tensor& g, const torch::Tensor& buf,
+                            const torch::Tensor& groups, const char* who) {
+  TORCH_CHECK(p.is_cuda(), who, ": p must be a GPU tensor");
+  flat_f32(p, p, who, "p"); flat_f32(g, p, who, "g"); flat_f32(buf, p, who, "buf");
+  TORCH_CHECK(p.numel() == g.numel() && p.numel() == buf.numel(), who, ": size mismatch");
+  TORCH_CHECK(p.numel() == t.n, who, ": the tables were built for buffers of ", t.n, " elements, got ", p.numel());
+  const GroupTable gt = group_table(groups, p, who);
+  TORCH_CHECK(t.max_group < gt.n, who, ": the tables name group ", t.max_group, ", the group table holds ", gt.n);
+  return gt;
+}
+
+void sgd(torch::Tensor p, torch::Tensor g, torch::Tensor buf, c10::optional<torch::Tensor> shadow, const SgdTables& tables,
+         torch::Tensor groups, c10::optional<torch::Tensor> clip, bool skip_nonfinite, c10::optional<torch::Tensor> ema,
+         c10::optional<torch::Tensor> ema_pair) {
+  const char* who = "sgd";
+  TORCH_CHECK(!tables.tiles, who, ": tables of the tile form (sgd_tiles) go to sgd_t");
+  const GroupTable gt = sgd_common(tables, p, g, buf, groups, who);
+  TORCH_CHECK(tables.seg_start.device() == p.device(), who, ": the tables are on another device");
+  uint16_t* sh = nullptr;
+  if (shadow.has_value() && shadow->defined()) {
+    flat_bf16(*shadow, p, 8, who, "shadow");
+    TORCH_CHECK(shadow->numel() == p.numel(), who, ": shadow must hold the parameters' ", p.numel(), " elements, got ", shadow->numel());
+    sh = reinterpret_cast<uint16_t*>(shadow->data_ptr());
+  }
+  const float* pc = opt_clip(clip, p, who);
+  const pvr::AdamEma ea = ema_args(p, ema, ema_pair, who);
+  check(pvr_sgd(p.data_ptr<float>(), g.data_ptr<float>(), buf.data_ptr<float>(), sh, p.numel(), tables.seg_start.data_ptr<int64_t>(),
+                tables.seg_group.data_ptr<int>(), (int)tables.seg_start.numel(), gt.dev, gt.host, gt.n, pc, skip_nonfinite ? 1 : 0, ea,
+                stream()),
+        who);
+}
+
+void sgd_t(torch::Tensor p, torch::Tensor g, torch::Tensor buf, torch::Tensor shadow, torch::Tensor shadow_t, const SgdTables& tables,
+           torch::Tensor groups, c10::optional<torch::Tensor> clip, bool skip_nonfinite, c10::optional<torch::Tensor> ema,
+           c10::optional<torch::Tensor> ema_pair) {
+  const char* who = "sgd_t";
+  TORCH_CHECK(tables.tiles, who, ": tables of the segment form (sgd_segments) go to sgd");
+  const GroupTable gt = sgd_common(tables, p, g, buf, groups, who);
+  TORCH_CHECK(tables.tmeta.device() == p.device(), who, ": the tables are on another device");
+  flat_bf16(shadow, p, 8, who, "shadow");
+  flat_bf16(shadow_t, p, 16, who, "shadow_t");
+  TORCH_CHECK(shadow.numel() == p.numel(), who, ": shadow must hold the parameters' ", p.numel(), " elements, got ", shadow.numel());
+  TORCH_CHECK(shadow_t.numel() == tables.nt, who, ": the tables were built for a shadow_t of ", tables.nt, " elements, got ",
+              shadow_t.numel());
+  const float* pc = opt_clip(clip, p, who);
+  const pvr::AdamEma ea = ema_args(p, ema, ema_pair, who);
+  check(pvr_sgd_t(p.data_ptr<float>(), g.data_ptr<float>(), buf.data_ptr<float>(), reinterpret_cast<uint16_t*>(shadow.data_ptr()),
+                  reinterpret_cast<uint16_t*>(shadow_t.data_ptr()), tables.tmeta.data_ptr<int64_t>(), (int)tables.tmeta.size(0),
+                  (int)tables.ntiles, tables.fmeta.data_ptr<int64_t>(), (int)tables.fmeta.size(0), tables.flat4, gt.dev, gt.host, gt.n,
+                  pc, skip_nonfinite ? 1 : 0, ea, stream()),
+        who);
+}
+
 // Classifier head forward: LayerNorm of each image's CLS row (token 0 of tokens [B*N][D] bf16) and
 // logits = LN(x) . W^T + bias in fp32. Returns {logits [B][C], xhat [B][D], rstd [B]} (the latter two
 // saved for head_bwd).
@@ -1784,6 +1928,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("clip"), py::arg("skip_nonfinite"), py::arg("seg_start") = py::none(), py::arg("seg_group") = py::none(),
         py::arg("shadow_t") = py::none(), py::arg("tmeta") = py::none(), py::arg("ntiles") = 0, py::arg("fmeta") = py::none(),
         py::arg("flat4") = 0, py::arg("ema") = py::none(), py::arg("ema_pair") = py::none());
+  py::class_<SgdTables>(m, "SgdTables", "host-checked segment or tile tables of the SGD kernels (sgd_segments / sgd_tiles)")
+      .def_readonly("tiles", &SgdTables::tiles)
+      .def_readonly("ntiles", &SgdTables::ntiles)
+      .def_readonly("flat4", &SgdTables::flat4)
+      .def_readonly("numel", &SgdTables::n);
+  m.def("sgd_blocks", []() { return pvr_sgd_blocks(); });
+  m.def("sgd_segments", &sgd_segments, py::arg("seg_start"), py::arg("seg_group"), py::arg("numel"), py::arg("device"));
+  m.def("sgd_tiles", &sgd_tiles, py::arg("tmeta"), py::arg("fmeta"), py::arg("numel"), py::arg("numel_t"), py::arg("device"));
+  m.def("sgd", &sgd, py::arg("p"), py::arg("g"), py::arg("buf"), py::arg("shadow"), py::arg("tables"), py::arg("groups"),
+        py::arg("clip"), py::arg("skip_nonfinite"), py::arg("ema") = py::none(), py::arg("ema_pair") = py::none());
+  m.def("sgd_t", &sgd_t, py::arg("p"), py::arg("g"), py::arg("buf"), py::arg("shadow"), py::arg("shadow_t"), py::arg("tables"),
+        py::arg("groups"), py::arg("clip"), py::arg("skip_nonfinite"), py::arg("ema") = py::none(), py::arg("ema_pair") = py::none());
   m.def("scale_by_clip", &scale_by_clip);
   m.def("head_fwd", &head_fwd);
   m.def("head_bwd", &head_bwd, py::arg("dlogits"), py::arg("xhat"), py::arg("rstd"), py::arg("gamma"), py::arg("beta"), py::arg("W"),

@@ -40,6 +40,10 @@ constexpr int LAMB_ALWAYS_ADAPT = 2;
 // Elements of one chunk of the LAMB norm pass: one workgroup, 4 float4 per thread
 constexpr int LAMB_CHUNK = 4096;
 
+// SGD (sgd.hip) reads the same table too: lr, beta1 as the momentum, weight_decay, and in word 7 this bit
+// for Nesterov momentum; every other column is ignored. A row with beta1 == 0 has no momentum buffer.
+constexpr int SGD_NESTEROV = 4;
+
 // A dropout site: the element's 16-bit hash of (*seed + offset) is kept iff >= thr = round(p * 65536);
 // kept values scale by 65536 / (65536 - thr). seed null: no dropout.
 struct DropSite {
@@ -340,6 +344,22 @@ hipError_t pvr_lamb_update(float* p, const float* m, const float* v, uint16_t* s
                            const int64_t* fmeta, int nflat, int64_t flat4, const float* trust, const pvr::AdamGroup* groups,
                            const pvr::AdamGroup* host_groups, int ngroups, const float* clip, int skip_nonfinite, pvr::AdamEma ema,
                            hipStream_t s);
+
+// ---- sgd.hip
+// SGD with momentum (torch.optim.SGD, dampening 0) on the flat buffers of pvr_adam, one launch: per element
+// g' = g * clip[1] (+ weight_decay * p), buf = beta1 * buf + g' (rows with beta1 != 0 only: buf of a row with
+// beta1 == 0 is neither read nor written), d = g' + beta1 * buf with SGD_NESTEROV, else buf (g' without
+// momentum), p -= lr * d; bf16 shadow, W^T and the model EMA as pvr_adam / pvr_adam_t write them.
+// pvr_sgd_blocks: the segment-table form's grid cap (its grid-stride loop covers blocks * 256 float4 per trip).
+int pvr_sgd_blocks();
+hipError_t pvr_sgd(float* p, const float* g, float* buf, uint16_t* shadow, int64_t n, const int64_t* seg_start, const int* seg_group,
+                   int nseg, const pvr::AdamGroup* groups, const pvr::AdamGroup* host_groups, int ngroups, const float* clip,
+                   int skip_nonfinite, pvr::AdamEma ema, hipStream_t s);
+// The tile form: pvr_adam_t's tables (tmeta int64 [nmat][6], fmeta int64 [nflat][4]).
+hipError_t pvr_sgd_t(float* p, const float* g, float* buf, uint16_t* shadow, uint16_t* shadow_t, const int64_t* tmeta, int nmat,
+                     int ntiles, const int64_t* fmeta, int nflat, int64_t flat4, const pvr::AdamGroup* groups,
+                     const pvr::AdamGroup* host_groups, int ngroups, const float* clip, int skip_nonfinite, pvr::AdamEma ema,
+                     hipStream_t s);
 
 // ---- fp8.hip
 hipError_t pvr_fp8_quant(const uint16_t* x, int64_t ldx, uint8_t* y, int64_t ldy, int64_t rows, int cols, const float* qscale,

@@ -10,7 +10,9 @@ part of this stack and there is no network, so the equivalent here is:
     pretrained weights run on the fused MI355X path; ``to_torchvision_state_dict`` is the inverse;
   * ``vit_from_torchvision_checkpoint``: build the matching ``ViT`` (LayerNorm eps 1e-6, as
     torchvision uses) and load the converted weights;
-  * ``feature_extractor``: freeze the backbone and install a fresh classifier head.
+  * ``feature_extractor``: freeze the backbone and install a fresh classifier head;
+  * ``resize_position_embedding`` / ``load_state_dict_resized``: weights trained at one resolution into a
+    model of another (the paper's fine-tuning at 384 px), the position grid resampled in 2-D.
 
 The key mapping covers both torchvision MLP naming schemes (``mlp.0`` / ``mlp.3`` and the older
 ``mlp.linear_1`` / ``mlp.linear_2``). Parity against real torchvision weights is unpinned (no
@@ -24,7 +26,9 @@ from typing import Dict, Optional
 import torch
 from torch import nn
 
-from .vit import ViT
+from .vit import RESIZE_MODES, ViT, resize_position_embedding  # noqa: F401
+
+POS_KEY = "patch_embedding_block.position_embedding"
 
 _LAYER_RE = re.compile(r"^encoder\.layers\.encoder_layer_(\d+)\.(.+)$")
 
@@ -114,9 +118,30 @@ def set_layernorm_eps(model: nn.Module, eps: float) -> nn.Module:
     return model
 
 
+def load_state_dict_resized(model: nn.Module, sd: Dict[str, torch.Tensor], mode: str = "bicubic", strict: bool = True):
+    """``model.load_state_dict(sd)`` for a checkpoint trained at another resolution: its position embedding
+    is resampled to the model's patch grid first (:func:`resize_position_embedding`, ``align_corners=False``;
+    torchvision's ``interpolate_embeddings`` uses ``align_corners=True`` and gives other values). Every other
+    shape must match as usual; a checkpoint of the model's own size loads exactly as ``load_state_dict`` does.
+    ``ValueError`` if the checkpoint's token count behind the class token is not a square. Returns
+    ``load_state_dict``'s result."""
+    pos = sd.get(POS_KEY)
+    if pos is not None:
+        n_new = model.patch_embedding_block.number_of_patches
+        g_new = int(round(n_new ** 0.5))
+        if pos.dim() == 3 and pos.shape[1] != n_new + 1:
+            sd = dict(sd)
+            sd[POS_KEY] = resize_position_embedding(pos, g_new, mode)
+    return model.load_state_dict(sd, strict=strict)
+
+
 def vit_from_torchvision_checkpoint(path: str, num_heads: Optional[int] = None, num_classes: Optional[int] = None,
                                     **overrides) -> ViT:
-    """Build a ViT from a local torchvision checkpoint file (loaded with ``weights_only=True``)."""
+    """Build a ViT from a local torchvision checkpoint file (loaded with ``weights_only=True``).
+
+    ``image_size=S`` (an override) builds the model at ``S`` from a checkpoint of another size: the position
+    embedding is resampled as :func:`load_state_dict_resized` does (``mode="bicubic"``, ``align_corners=False``,
+    unlike torchvision's own ``interpolate_embeddings``, which pins the corners)."""
     sd = torch.load(path, map_location="cpu", weights_only=True)
     if "state_dict" in sd and isinstance(sd["state_dict"], dict):
         sd = sd["state_dict"]
@@ -128,7 +153,7 @@ def vit_from_torchvision_checkpoint(path: str, num_heads: Optional[int] = None, 
     model = set_layernorm_eps(ViT(**cfg), TORCHVISION_LN_EPS)
     keep_head = head_classes is not None and head_classes == cfg["num_classes"]
     ours = from_torchvision_state_dict(sd, drop_head=not keep_head)
-    missing, unexpected = model.load_state_dict(ours, strict=False)
+    missing, unexpected = load_state_dict_resized(model, ours, strict=False)
     allowed_missing = set() if keep_head else {"classifier.0.weight", "classifier.0.bias"}
     if set(missing) - allowed_missing or unexpected:
         raise RuntimeError(f"checkpoint mismatch: missing {missing}, unexpected {unexpected}")

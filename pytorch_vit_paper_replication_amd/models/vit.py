@@ -37,6 +37,38 @@ def patch_keep_count(n_p: int, rate: float) -> int:
     return max(1, n_p - int(math.floor(rate * n_p)))
 
 
+RESIZE_MODES = ("bicubic", "bilinear")
+
+
+def resize_position_embedding(pos: torch.Tensor, new_grid: int, mode: str = "bicubic") -> torch.Tensor:
+    """A position embedding ``[1, g * g + 1, D]`` (class-token row first) on a ``new_grid x new_grid`` patch grid:
+    rows ``1..`` are viewed as ``[1, D, g, g]`` in fp32 and resampled with
+    ``F.interpolate(grid, size=(new_grid, new_grid), mode=mode, align_corners=False)``; row 0 is copied. Returns a
+    new tensor in ``pos``'s dtype (a clone for the same grid). ``ValueError`` if the rows behind the class token do
+    not form a square grid.
+
+    torchvision's own ``interpolate_embeddings`` resamples with ``align_corners=True`` (grid corners pinned); this
+    one does not (pixel-centre alignment, what timm and the released ViT fine-tuning code do), so the two differ
+    away from the grid's centre."""
+    if mode not in RESIZE_MODES:
+        raise ValueError(f"mode must be one of {RESIZE_MODES}, got {mode!r}")
+    if pos.dim() != 3 or pos.shape[0] != 1 or pos.shape[1] < 2:
+        raise ValueError(f"position embedding must be [1, g * g + 1, D], got {tuple(pos.shape)}")
+    n, D = pos.shape[1] - 1, pos.shape[2]
+    g = math.isqrt(n)
+    if g * g != n:
+        raise ValueError(f"{n} patch rows behind the class token do not form a square grid")
+    new_grid = int(new_grid)
+    if new_grid <= 0:
+        raise ValueError(f"new_grid must be positive, got {new_grid}")
+    if new_grid == g:
+        return pos.detach().clone()
+    grid = pos[:, 1:].detach().float().reshape(1, g, g, D).permute(0, 3, 1, 2)
+    new = F.interpolate(grid, size=(new_grid, new_grid), mode=mode, align_corners=False)
+    new = new.permute(0, 2, 3, 1).reshape(1, new_grid * new_grid, D).to(pos.dtype)
+    return torch.cat((pos[:, :1].detach(), new), dim=1)
+
+
 class PatchEmbedding(nn.Module):
     """Image -> [B, N+1, D] patch + CLS + position embeddings (reference models/vit.py:5-67).
 
@@ -435,6 +467,43 @@ class ViT(nn.Module):
         n_keep = patch_keep_count(pe.number_of_patches, rate)
         pe.patch_keep = n_keep if n_keep < pe.number_of_patches else 0
         self.config["patch_dropout"] = float(rate)
+        return self
+
+    # ------------------------------------------------------------------ resolution
+    def set_image_size(self, image_size: int, mode: str = "bicubic") -> "ViT":
+        """Change the model's input resolution, as the paper does between pre-training and fine-tuning: the
+        patch rows of ``position_embedding`` are resampled in 2-D from the old ``g x g`` patch grid to the new
+        one (:func:`resize_position_embedding`: ``F.interpolate(..., mode=mode, align_corners=False)`` on the
+        fp32 ``[1, D, g, g]`` view; ``mode`` is ``"bicubic"`` or ``"bilinear"``) and the class-token row is
+        copied. The parameter is replaced by one of the new shape, ``number_of_patches`` and
+        ``config["image_size"]`` follow, a patch-dropout rate is re-applied to the new patch count; the
+        constructor signature and the state-dict keys are unchanged. The same size is a no-op that keeps
+        the parameter and its bits.
+
+        Call it before the optimizer is built and before the first fused forward: with a ``ParamStore``
+        already covering the model it raises ``RuntimeError``. ``ValueError`` for a size the patch size does
+        not divide."""
+        pe = self.patch_embedding_block
+        P = int(pe.patch_size)
+        image_size = int(image_size)
+        if image_size <= 0 or image_size % P != 0:
+            raise ValueError(f"image size {image_size} is not a positive multiple of the patch size {P}")
+        if mode not in RESIZE_MODES:
+            raise ValueError(f"mode must be one of {RESIZE_MODES}, got {mode!r}")
+        g_new = image_size // P
+        if g_new * g_new == pe.number_of_patches and image_size == self.config["image_size"]:
+            return self
+        st = getattr(self, "_pvr_store", None)
+        if st is not None and st.covers(self):
+            raise RuntimeError("set_image_size() must run before the first fused forward and before the optimizer is "
+                               "built: a ParamStore already covers this model's parameters")
+        old = pe.position_embedding
+        new = resize_position_embedding(old.detach(), g_new, mode)
+        pe.position_embedding = nn.Parameter(new, requires_grad=old.requires_grad)
+        pe.number_of_patches = g_new * g_new
+        self.config["image_size"] = image_size
+        if self.config.get("patch_dropout"):
+            self.set_patch_dropout(self.config["patch_dropout"])
         return self
 
     # ------------------------------------------------------------------ uint8 input
